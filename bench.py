@@ -14,7 +14,10 @@ per GPU); nothing else runs in the timed region.  ``python bench.py --gpus N`` s
 processes itself (``launch_ranks``: one per GPU, rendezvous on 127.0.0.1); ``torchrun --nproc-per-node N
 bench.py --gpus N`` works the same way (every rank checks WORLD_SIZE == --gpus).
 
-Also reported (each in its own pass, outside the headline's timed region):
+A plain run (``bench.py --gpus N --steps K --warmup W``) sets up, warms up, times the K steps and prints the
+result line; ``--dump-outputs DIR`` also writes what the last timed step returned (``DIR/proba.npy``, float32).
+
+With ``--full`` also reported (each in its own pass, outside the headline's timed region; null in a plain run):
 ``roofline`` of the dominant kernel (sample-axis attention, bf16 MFMA; algorithmic
 flops 4*T*Nq*Nk*E per launch; every launch of a separate pass of the same steps
 bracketed by HIP events on its lane stream, mmpfn_kernel_timing), ``f32_parity_mode``
@@ -68,6 +71,11 @@ def parse():
                    help="f16: MMPFN_PREC_F16, the reference's fp16 autocast (fp16 state + operands); bf16: bf16 "
                         "operands on an fp32 state; f32: the parity mode")
     p.add_argument("--members", type=int, default=MEMBERS_PER_GPU, help="members per GPU")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline, also run every other leg (roofline, other precisions, API, KV cache, "
+                        "configs B / D / E, modality towers, CPU baselines); the --no-* options prune them")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step returned (the class probabilities) to DIR/proba.npy")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--attn-reps", type=int, default=20)
     p.add_argument("--lanes", type=int, default=None, help="concurrent member lanes per GPU (default: engine's)")
@@ -431,9 +439,9 @@ def _lib_prec(f32: bool) -> int:
     return _lib.PREC_F32 if f32 else _lib.autocast_precision()
 
 
-def timed_steps(step, steps, warmup, world, device):
+def timed_steps(step, steps, warmup, world, device, last=None):
     """W untimed steps, then K steps bracketed by barrier + synchronize on both sides; the max
-    wall time over ranks (bench contract)."""
+    wall time over ranks (bench contract).  ``last``: a list that receives what the last timed step returned."""
     import torch.distributed as dist
 
     for _ in range(warmup):
@@ -442,12 +450,15 @@ def timed_steps(step, steps, warmup, world, device):
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    out = None
     for _ in range(steps):
-        step()
+        out = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
+    if last is not None and steps > 0:
+        last.append(out)
     if world > 1:
         tt = torch.tensor([dt], device=device if dist.get_backend() == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -715,55 +726,22 @@ def launch_ranks(n: int, cmd: list[str], stdout=None, poll_s: float = 0.2) -> in
     return rc
 
 
-def main():
-    args = parse()
-    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # plain `python bench.py --gpus N`: become the launcher of N rank processes (torchrun's job)
-        sys.exit(launch_ranks(args.gpus, [sys.executable, "-u", str(Path(__file__).resolve()), *sys.argv[1:]]))
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    if world != args.gpus:
-        raise SystemExit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}: the world must be one rank per GPU")
-    rank = int(os.environ.get("RANK", "0"))
-    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    # rehearsal knobs for a multi-rank run on a box with fewer GPUs than ranks (not for measurement):
-    # MMPFN_BENCH_SHARE_GPUS=1 maps ranks onto the visible GPUs round-robin, MMPFN_BENCH_BACKEND=gloo
-    # replaces RCCL (which refuses two ranks on one GPU)
-    if os.environ.get("MMPFN_BENCH_SHARE_GPUS") == "1":
-        local_rank %= torch.cuda.device_count()
-    backend = os.environ.get("MMPFN_BENCH_BACKEND", "nccl")
-    torch.cuda.set_device(local_rank)
-    device = torch.device("cuda", local_rank)
-    import torch.distributed as dist
+def dump_outputs(out_dir, probs):
+    """``--dump-outputs DIR``: what the caller of the last timed step received, the ensemble's class
+    probabilities of the Q query rows ([Q, N_CLASSES]), as ``DIR/proba.npy`` in float32.  The workload is
+    seeded (build_workload), so two builds run with the same arguments can be compared array for array."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    np.save(out_dir / "proba.npy", probs.detach().to("cpu", torch.float32).numpy())
 
-    if world > 1:
-        dist.init_process_group(backend, device_id=device if backend == "nccl" else None)
 
+def engine_legs(args, eng, step, cfg, sd, x, y, image, members, mine, assignment, rank, world, device, img, prec, T):
+    """``--full``: the legs that run on the headline's engine, each in a pass of its own after the headline's
+    timed region: the live roofline of the dominant kernel, the other 16-bit mode, the fp32 parity mode, the
+    classifier API from host numpy, fit_with_cache serving and the isolated attention launches."""
     from multimodalpfn_amd import _lib
-    from multimodalpfn_amd.parallel import lpt_assign, member_cost
 
-    prec = {"f16": _lib.PREC_F16, "bf16": _lib.PREC_BF16, "f32": _lib.PREC_F32}[args.precision]
-    # the classifier legs (api_end_to_end) run inference_precision="auto" = the reference's fp16 autocast
-    os.environ["MMPFN_AUTOCAST"] = "f16" if prec == _lib.PREC_F16 else "bf16"
-    cfg, sd, model, x, y, image, members = build_workload(device, world, args.members)
-    eng = model.engine(device)
-    img = torch.from_numpy(image).to(device)
     M = len(members)
-    T = (N_FEAT + 1) // 2 + CAP + 1
-    assignment = lpt_assign([member_cost(T, S_ROWS, N_TRAIN)] * M, world, [T] * M, args.batch or eng.batch)
-    mine = assignment[rank]
-    step = make_step(eng, members, mine, assignment, rank, img, prec, args.lanes, args.batch, args.mixer_stream)
-
-    probs = step()
-    eng.status()  # NaN check once (reference raises ValueError)
-    assert torch.isfinite(probs).all()
-    # ---- headline: nothing but the steps in the timed region
-    dt = timed_steps(step, args.steps, args.warmup, world, device)
-    rows = M * S_ROWS * args.steps
-    value = rows / dt
-    step_flop = len(mine) * forward_flops(T) + mixer_flops()  # per rank
-    wf = step_flop * args.steps / dt / 1e12  # TFLOP/s of one rank (its wall time is the job's max)
-
     # ---- live roofline of the dominant kernel: a SEPARATE pass of the same steps with every
     #      attention launch bracketed by HIP events on its lane stream (kept out of the headline)
     #      Two such passes: the headline's own lane setting (launches share the CUs with the other
@@ -874,7 +852,13 @@ def main():
                         "random q / k: ~10 % of the waves fail the e4m3 range checks (first-tile scale, DESIGN 5.8) and "
                         "repeat their queries on the exact non-pipelined path (~4x a pipelined pass); e5m2 never does; "
                         "the model's own scores: config_E's 'f16 + fp8 P.V (e4m3)' step")
-    eng.close()
+    return {"roofline": roof, "api_end_to_end": api, "api_end_to_end_default_preprocessing": api_def,
+            "other_16bit_mode": other16, "f32_parity_mode": f32, "kv_cache_predict": kv}
+
+
+def other_legs(args, sd, x, y, image, rank, world, device, prec):
+    """``--full``: the legs that build engines or models of their own (configs D, B and E, the modality
+    towers) and the CPU baselines; they run after the headline's engine is closed."""
     cfg_d = config_d_leg(device, world, rank, args, prec) if args.config_d else None
     cfg_b = None
     if args.config_b and rank == 0:
@@ -899,6 +883,73 @@ def main():
         cpu = cpu_baseline(sd, x, y, image, use_sdpa=True)
         if args.cpu_einsum:
             cpu_e = cpu_baseline(sd, x, y, image, use_sdpa=False)
+    return {"cpu_baseline": cpu, "cpu_baseline_einsum": cpu_e, "config_B": cfg_b, "config_D": cfg_d,
+            "config_E": cfg_e, "modality_encoders": mod}
+
+
+def main():
+    args = parse()
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        # plain `python bench.py --gpus N`: become the launcher of N rank processes (torchrun's job)
+        sys.exit(launch_ranks(args.gpus, [sys.executable, "-u", str(Path(__file__).resolve()), *sys.argv[1:]]))
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    if world != args.gpus:
+        raise SystemExit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}: the world must be one rank per GPU")
+    rank = int(os.environ.get("RANK", "0"))
+    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    # rehearsal knobs for a multi-rank run on a box with fewer GPUs than ranks (not for measurement):
+    # MMPFN_BENCH_SHARE_GPUS=1 maps ranks onto the visible GPUs round-robin, MMPFN_BENCH_BACKEND=gloo
+    # replaces RCCL (which refuses two ranks on one GPU)
+    if os.environ.get("MMPFN_BENCH_SHARE_GPUS") == "1":
+        local_rank %= torch.cuda.device_count()
+    backend = os.environ.get("MMPFN_BENCH_BACKEND", "nccl")
+    torch.cuda.set_device(local_rank)
+    device = torch.device("cuda", local_rank)
+    import torch.distributed as dist
+
+    if world > 1:
+        dist.init_process_group(backend, device_id=device if backend == "nccl" else None)
+
+    from multimodalpfn_amd import _lib
+    from multimodalpfn_amd.parallel import lpt_assign, member_cost
+
+    prec = {"f16": _lib.PREC_F16, "bf16": _lib.PREC_BF16, "f32": _lib.PREC_F32}[args.precision]
+    # the classifier legs (api_end_to_end) run inference_precision="auto" = the reference's fp16 autocast
+    os.environ["MMPFN_AUTOCAST"] = "f16" if prec == _lib.PREC_F16 else "bf16"
+    cfg, sd, model, x, y, image, members = build_workload(device, world, args.members)
+    eng = model.engine(device)
+    img = torch.from_numpy(image).to(device)
+    M = len(members)
+    T = (N_FEAT + 1) // 2 + CAP + 1
+    assignment = lpt_assign([member_cost(T, S_ROWS, N_TRAIN)] * M, world, [T] * M, args.batch or eng.batch)
+    mine = assignment[rank]
+    step = make_step(eng, members, mine, assignment, rank, img, prec, args.lanes, args.batch, args.mixer_stream)
+
+    probs = step()
+    eng.status()  # NaN check once (reference raises ValueError)
+    assert torch.isfinite(probs).all()
+    # ---- headline: nothing but the steps in the timed region
+    last = []
+    dt = timed_steps(step, args.steps, args.warmup, world, device, last)
+    rows = M * S_ROWS * args.steps
+    value = rows / dt
+    step_flop = len(mine) * forward_flops(T) + mixer_flops()  # per rank
+    wf = step_flop * args.steps / dt / 1e12  # TFLOP/s of one rank (its wall time is the job's max)
+    batch = eng.batch if args.batch is None else args.batch
+    if args.dump_outputs and rank == 0 and last:
+        dump_outputs(args.dump_outputs, last[0])
+
+    # ---- everything else the benchmark measures: --full only (a plain run reports these as null)
+    legs = dict.fromkeys(("roofline", "cpu_baseline", "cpu_baseline_einsum", "api_end_to_end",
+                          "api_end_to_end_default_preprocessing", "other_16bit_mode", "f32_parity_mode", "config_B",
+                          "config_D", "config_E", "kv_cache_predict", "modality_encoders"))
+    if args.full:
+        legs.update(engine_legs(args, eng, step, cfg, sd, x, y, image, members, mine, assignment, rank, world, device,
+                                img, prec, T))
+    eng.close()
+    if args.full:
+        legs.update(other_legs(args, sd, x, y, image, rank, world, device, prec))
     if rank == 0:
         line = {
             "metric": METRIC,
@@ -934,7 +985,7 @@ def main():
                 "parallelism": f"ensemble members sharded over {world} GPU(s) + RCCL all-gather of logits",
                 "operands": OPERANDS[{_lib.PREC_F16: "f16", _lib.PREC_BF16: "bf16"}.get(prec, "f32")],
             },
-            "roofline": roof,
+            "roofline": legs["roofline"],
             "whole_forward": {
                 "tflop_per_step_per_gpu": round(step_flop / 1e12, 3),
                 "achieved": round(wf, 1),
@@ -942,17 +993,7 @@ def main():
                 "frac": round(wf / BF16_PEAK_TFLOPS, 4),
                 "note": "algorithmic flops of the mixer + every member's 12-layer stack (SURVEY.md 8d) / step time",
             },
-            "cpu_baseline": cpu,
-            "cpu_baseline_einsum": cpu_e,
-            "api_end_to_end": api,
-            "api_end_to_end_default_preprocessing": api_def,
-            "other_16bit_mode": other16,
-            "f32_parity_mode": f32,
-            "config_B": cfg_b,
-            "config_D": cfg_d,
-            "config_E": cfg_e,
-            "kv_cache_predict": kv,
-            "modality_encoders": mod,
+            **{k: v for k, v in legs.items() if k != "roofline"},
         }
         print(json.dumps(line))
     if world > 1:
