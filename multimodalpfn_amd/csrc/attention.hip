@@ -880,23 +880,24 @@ namespace {
 std::atomic<int> g_x3_cheap_min_keys{X3_CHEAP_MIN_KEYS};
 std::atomic<int> g_x3_cheap_form{X3_CHEAP_FORM};  // attn_item3_kernel's CHEAP bits on those sequences
 
-hipError_t launch_item_attention(const void* q, const void* k, const void* vt, void* out, int S, int T, int H,
-                                 int Npad, int nk, int a0, int na, int b0, int nb, int kvb, hipStream_t st,
-                                 int64_t kv_bstride, bool q_prescaled, bool x3, const void* vt8 = nullptr,
-                                 int f8 = 0, bool qk_f16 = false, bool o_f16 = false) {
+// x3: the parity mode's kernel (fp32 operands; no prescale, fp8 or 16-bit element types)
+hipError_t launch_item_attention(const AttnLayerArgs& l, bool x3, hipStream_t st) {
+  const int T = l.T, H = l.H, Npad = l.Npad, nk = l.nk, na = l.na, nb = l.nb, kvb = l.kvb;
   if (na + nb <= 0 || T <= 0) return hipSuccess;
   if (nk <= 0 || Npad % A2_KT != 0 || nk > Npad || H > 8 || H <= 0) return hipErrorInvalidValue;
   if (nb > 0 && (kvb < 0 || kvb >= H)) return hipErrorInvalidValue;
+  if (l.qk_t == DType::F32 || l.o_t == DType::F32 || (l.qk_t == DType::F16 && l.o_t != DType::F16))
+    return hipErrorInvalidValue;
   Attn2Args a;
-  a.q = (const bf16*)q, a.k = (const bf16*)k, a.vt = (const bf16*)vt, a.o = (bf16*)out;
-  a.S = S, a.H = H, a.Npad = Npad, a.nk = nk;
-  a.a0 = a0, a.na = na, a.b0 = b0, a.nb = nb, a.kvb = nb > 0 ? kvb : -1;
-  a.kv_bstride = kv_bstride > 0 ? kv_bstride : (int64_t)H * Npad * 32;
-  a.q_prescaled = q_prescaled ? 1 : 0;
-  a.vt8 = (const unsigned char*)vt8, a.f8 = x3 ? 0 : f8;
-  a.qk_f16 = (!x3 && qk_f16) ? 1 : 0;
-  a.o_f16 = (!x3 && (qk_f16 || o_f16)) ? 1 : 0;
-  if (kv_bstride > 0 && (na > 0 || kvb != 0)) return hipErrorInvalidValue;  // cache layout holds head 0 only
+  a.q = (const bf16*)l.q, a.k = (const bf16*)l.k, a.vt = (const bf16*)l.vt, a.o = (bf16*)l.out;
+  a.S = l.S, a.H = H, a.Npad = Npad, a.nk = nk;
+  a.a0 = l.a0, a.na = na, a.b0 = l.b0, a.nb = nb, a.kvb = nb > 0 ? kvb : -1;
+  a.kv_bstride = l.kv_bstride > 0 ? l.kv_bstride : (int64_t)H * Npad * 32;
+  a.q_prescaled = !x3 && l.q_prescaled ? 1 : 0;
+  a.vt8 = (const unsigned char*)l.vt8, a.f8 = x3 ? 0 : l.f8;
+  a.qk_f16 = (!x3 && l.qk_t == DType::F16) ? 1 : 0;
+  a.o_f16 = (!x3 && l.o_t == DType::F16) ? 1 : 0;
+  if (l.kv_bstride > 0 && (na > 0 || kvb != 0)) return hipErrorInvalidValue;  // cache layout holds head 0 only
   const int qpb = x3 ? A3_QPB : ATTN_ITEM_QPB;
   int acc = 0;
   for (int g = 0; g < H; ++g) {
@@ -923,22 +924,14 @@ hipError_t launch_item_attention(const void* q, const void* k, const void* vt, v
 
 }  // namespace
 
-hipError_t launch_attn_layer(const void* q, const void* k, const void* vt, void* out, int S, int T, int H, int Npad,
-                             int nk, int a0, int na, int b0, int nb, int kvb, hipStream_t st, int64_t kv_bstride,
-                             bool q_prescaled, const void* vt8, int f8, bool qk_f16, bool o_f16) {
-  return launch_item_attention(q, k, vt, out, S, T, H, Npad, nk, a0, na, b0, nb, kvb, st, kv_bstride, q_prescaled,
-                               false, vt8, f8, qk_f16, o_f16);
-}
+hipError_t launch_attn_layer(const AttnLayerArgs& a, hipStream_t st) { return launch_item_attention(a, false, st); }
 
 int set_x3_cheap_min_keys(int n, int form) {
   if (form >= 1 && form <= 3) g_x3_cheap_form.store(form);
   return g_x3_cheap_min_keys.exchange(n);
 }
 
-hipError_t launch_attn_item3(const void* q, const void* k, const void* vt, void* out, int S, int T, int H, int Npad,
-                             int nk, int a0, int na, int b0, int nb, int kvb, hipStream_t st, int64_t kv_bstride) {
-  return launch_item_attention(q, k, vt, out, S, T, H, Npad, nk, a0, na, b0, nb, kvb, st, kv_bstride, false, true);
-}
+hipError_t launch_attn_item3(const AttnLayerArgs& a, hipStream_t st) { return launch_item_attention(a, true, st); }
 
 hipError_t launch_attn(const AttnArgs& a, int batches, int prec, int nw, hipStream_t st) {
   if (a.nq <= 0 || batches <= 0) return hipSuccess;
@@ -952,12 +945,13 @@ hipError_t launch_attn(const AttnArgs& a, int batches, int prec, int nw, hipStre
   if (a.nk <= 0 || a.kpad % IA_KT != 0 || a.nk > a.kpad) return hipErrorInvalidValue;
   if (nw != 1 && nw != 4) return hipErrorInvalidValue;
   dim3 grid((a.nq + 32 * nw - 1) / (32 * nw), a.H, batches);
+  // four waves per block: PREC_F32_MFMA's item attention only (launch_attn_item; the other modes' item attention
+  // runs launch_item_attention)
+  if (nw == 4 && prec != PREC_F32_MFMA) return hipErrorInvalidValue;
   if (prec == PREC_BF16) {
-    if (nw == 4) hipLaunchKernelGGL((attn_item_kernel<1, 4>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((attn_item_kernel<1, 1>), grid, dim3(64), 0, st, a);
+    hipLaunchKernelGGL((attn_item_kernel<1, 1>), grid, dim3(64), 0, st, a);
   } else if (prec == PREC_F32) {  // parity mode: split-bf16 products (the feature attention's path)
-    if (nw == 4) hipLaunchKernelGGL((attn_item_kernel<2, 4>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((attn_item_kernel<2, 1>), grid, dim3(64), 0, st, a);
+    hipLaunchKernelGGL((attn_item_kernel<2, 1>), grid, dim3(64), 0, st, a);
   } else {
     if (nw == 4) hipLaunchKernelGGL((attn_item_kernel<0, 4>), grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((attn_item_kernel<0, 1>), grid, dim3(64), 0, st, a);
@@ -976,11 +970,11 @@ hipError_t launch_attn_item(const void* q, const void* k, const void* vt, void* 
   a.o_bstride = S, a.o_qstride = 1;
   a.s0 = s0, a.nq = nq, a.nk = nk, a.kvh_fixed = kv_head_fixed, a.H = H;
   if (prec == PREC_BF16 || prec == PREC_F32) {
-    const bool x3 = prec == PREC_F32;
-    if (kv_head_fixed < 0)
-      return launch_item_attention(q, k, vt, out, S, T, H, Npad, nk, s0, nq, 0, 0, -1, st, kv_bstride, false, x3);
-    return launch_item_attention(q, k, vt, out, S, T, H, Npad, nk, 0, 0, s0, nq, kv_head_fixed, st, kv_bstride, false,
-                                 x3);
+    AttnLayerArgs l{q, k, vt, out, S, T, H, Npad, nk};
+    if (kv_head_fixed < 0) l.a0 = s0, l.na = nq, l.b0 = 0, l.nb = 0, l.kvb = -1;
+    else l.a0 = 0, l.na = 0, l.b0 = s0, l.nb = nq, l.kvb = kv_head_fixed;
+    l.kv_bstride = kv_bstride;
+    return launch_item_attention(l, prec == PREC_F32, st);
   }
   return launch_attn(a, T, prec, 4, st);
 }

@@ -24,29 +24,17 @@
 #include <vector>
 
 #include "../../include/mmpfn_modality.h"
+#include "devbuf.h"
 #include "modality.h"
 
 using namespace mmpfn;
 
 namespace {
 
-struct Buf {
-  void* p = nullptr;
-  size_t bytes = 0;
-};
-
-uint16_t to_bf16_bits(float f) {  // round-to-nearest-even, NaN preserving
-  uint32_t u;
-  std::memcpy(&u, &f, 4);
-  if ((u & 0x7fffffff) > 0x7f800000) return (uint16_t)((u >> 16) | 0x40);
-  u += 0x7fff + ((u >> 16) & 1);
-  return (uint16_t)(u >> 16);
-}
-
 struct EncLayer {
   // ViT: ln1 = norm1, ln2 = norm2 (pre-LN); text: ln1 = attention.output.LayerNorm, ln2 = output.LayerNorm
-  Buf ln1g, ln1b, ln2g, ln2b, ls1, ls2;
-  Buf qkv, qkv_h, qkv_b, proj, proj_h, proj_b, fc1, fc1_h, fc1_b, fc2, fc2_h, fc2_b;
+  DevBuf ln1g, ln1b, ln2g, ln2b, ls1, ls2;
+  DevBuf qkv, qkv_h, qkv_b, proj, proj_h, proj_b, fc1, fc1_h, fc1_b, fc2, fc2_h, fc2_b;
 };
 
 }  // namespace
@@ -58,80 +46,25 @@ struct mmpfn_enc {
   bool have_model = false, finalized = false;
   mmpfn_enc_desc d{};
   std::map<std::string, std::vector<float>> host;
-  std::vector<Buf*> owned;
   std::vector<EncLayer> layers;
   int Kpad = 0;  // ViT patch GEMM K (C * P * P rounded up to 64)
-  Buf pe_w, pe_wh, pe_b, cls_tok, pos, norm_g, norm_b;
-  std::map<std::pair<int, int>, Buf> pos_cache;  // interpolated pos_embed per (grid h, grid w)
-  Buf wemb, pemb, temb, emb_g, emb_b, eproj, eproj_h, eproj_b;
+  DevBuf pe_w, pe_wh, pe_b, cls_tok, pos, norm_g, norm_b;
+  std::map<std::pair<int, int>, DevBuf> pos_cache;  // interpolated pos_embed per (grid h, grid w)
+  DevBuf wemb, pemb, temb, emb_g, emb_b, eproj, eproj_h, eproj_b;
   // workspace
-  Buf X, A, QKV, O, Hh, Y, Xc, Ac, Oc, Hc, Yc, kb, flag, P0;
+  DevBuf X, A, QKV, O, Hh, Y, Xc, Ac, Oc, Hc, Yc, kb, flag, P0;
 };
 
 namespace {
 
-int fail(mmpfn_enc* e, int code, const std::string& msg) {
-  if (e) e->err = msg;
-  return code;
-}
-
-#define HIPCHK(expr)                                                                                 \
-  do {                                                                                               \
-    hipError_t e_ = (expr);                                                                          \
-    if (e_ != hipSuccess) return fail(enc, MMPFN_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-#define RC(expr)                      \
-  do {                                \
-    int rc_ = (expr);                 \
-    if (rc_ != MMPFN_OK) return rc_;  \
-  } while (0)
-
-int ensure(mmpfn_enc* enc, Buf& b, size_t bytes) {
-  if (b.bytes >= bytes && b.p) return MMPFN_OK;
-  if (b.p) HIPCHK(hipFree(b.p));
-  b.p = nullptr, b.bytes = 0;
-  bytes = (bytes + 255) & ~size_t(255);
-  HIPCHK(hipMalloc(&b.p, bytes));
-  b.bytes = bytes;
-  return MMPFN_OK;
-}
-
-int upload(mmpfn_enc* enc, Buf& b, const std::vector<float>& v, bool as_bf16) {
-  if (as_bf16) {
-    std::vector<uint16_t> h(v.size());
-    for (size_t i = 0; i < v.size(); ++i) h[i] = to_bf16_bits(v[i]);
-    RC(ensure(enc, b, h.size() * 2));
-    HIPCHK(hipMemcpy(b.p, h.data(), h.size() * 2, hipMemcpyHostToDevice));
-  } else {
-    RC(ensure(enc, b, v.size() * 4));
-    HIPCHK(hipMemcpy(b.p, v.data(), v.size() * 4, hipMemcpyHostToDevice));
-  }
-  return MMPFN_OK;
-}
-
-const std::vector<float>* getw(mmpfn_enc* enc, const std::string& name, size_t numel) {
-  auto it = enc->host.find(name);
-  if (it == enc->host.end()) {
-    enc->err = "missing weight: " + name;
-    return nullptr;
-  }
-  if (it->second.size() != numel) {
-    enc->err = "weight " + name + " has " + std::to_string(it->second.size()) + " elements, expected " +
-               std::to_string(numel);
-    return nullptr;
-  }
-  return &it->second;
-}
-
-#define GETW(var, name, n)                                  \
-  const std::vector<float>* var = getw(enc, (name), (n));   \
-  if (!var) return MMPFN_ERR_WEIGHT;
+#define HIPCHK(expr) HIPCHK_ON(enc, expr)
+#define GETW(var, name, n) GETW_ON(enc, var, name, n)
 
 // a Linear's weight in both dtypes (fp32 for the parity mode, bf16 for the MFMA path) + bias
-int up_linear(mmpfn_enc* enc, Buf& w, Buf& wh, Buf& b, const std::vector<float>& wv, const std::vector<float>& bv) {
-  RC(upload(enc, w, wv, false));
-  RC(upload(enc, wh, wv, true));
-  RC(upload(enc, b, bv, false));
+int up_linear(mmpfn_enc* enc, DevBuf& w, DevBuf& wh, DevBuf& b, const std::vector<float>& wv, const std::vector<float>& bv) {
+  RC(upload(enc, w, wv));
+  RC(upload(enc, wh, wv, DType::BF16));
+  RC(upload(enc, b, bv));
   return MMPFN_OK;
 }
 
@@ -153,12 +86,13 @@ int finalize_vit(mmpfn_enc* enc) {
     GETW(p, "pos_embed", (size_t)(1 + M * M) * D);
     GETW(g, "norm.weight", (size_t)D);
     GETW(b, "norm.bias", (size_t)D);
-    RC(upload(enc, enc->cls_tok, *c, false));
-    RC(upload(enc, enc->pos, *p, false));
-    RC(upload(enc, enc->norm_g, *g, false));
-    RC(upload(enc, enc->norm_b, *b, false));
+    RC(upload(enc, enc->cls_tok, *c));
+    RC(upload(enc, enc->pos, *p));
+    RC(upload(enc, enc->norm_g, *g));
+    RC(upload(enc, enc->norm_b, *b));
   }
-  enc->layers.assign(d.depth, EncLayer{});
+  enc->layers.clear();
+  enc->layers.resize(d.depth);
   for (int i = 0; i < d.depth; ++i) {
     const std::string pre = "blocks." + std::to_string(i) + ".";
     EncLayer& L = enc->layers[i];
@@ -174,10 +108,10 @@ int finalize_vit(mmpfn_enc* enc) {
     GETW(f1b, pre + "mlp.fc1.bias", F);
     GETW(f2w, pre + "mlp.fc2.weight", (size_t)D * F);
     GETW(f2b, pre + "mlp.fc2.bias", D);
-    RC(upload(enc, L.ln1g, *n1g, false));
-    RC(upload(enc, L.ln1b, *n1b, false));
-    RC(upload(enc, L.ln2g, *n2g, false));
-    RC(upload(enc, L.ln2b, *n2b, false));
+    RC(upload(enc, L.ln1g, *n1g));
+    RC(upload(enc, L.ln1b, *n1b));
+    RC(upload(enc, L.ln2g, *n2g));
+    RC(upload(enc, L.ln2b, *n2b));
     RC(up_linear(enc, L.qkv, L.qkv_h, L.qkv_b, *qw, *qb));
     RC(up_linear(enc, L.proj, L.proj_h, L.proj_b, *pw, *pb));
     RC(up_linear(enc, L.fc1, L.fc1_h, L.fc1_b, *f1w, *f1b));
@@ -185,8 +119,8 @@ int finalize_vit(mmpfn_enc* enc) {
     if (d.layerscale) {
       GETW(g1, pre + "ls1.gamma", D);
       GETW(g2, pre + "ls2.gamma", D);
-      RC(upload(enc, L.ls1, *g1, false));
-      RC(upload(enc, L.ls2, *g2, false));
+      RC(upload(enc, L.ls1, *g1));
+      RC(upload(enc, L.ls2, *g2));
     }
   }
   return MMPFN_OK;
@@ -201,18 +135,19 @@ int finalize_text(mmpfn_enc* enc) {
     GETW(t, "embeddings.token_type_embeddings.weight", (size_t)d.type_vocab * E);
     GETW(g, "embeddings.LayerNorm.weight", E);
     GETW(b, "embeddings.LayerNorm.bias", E);
-    RC(upload(enc, enc->wemb, *w, false));
-    RC(upload(enc, enc->pemb, *p, false));
-    RC(upload(enc, enc->temb, *t, false));
-    RC(upload(enc, enc->emb_g, *g, false));
-    RC(upload(enc, enc->emb_b, *b, false));
+    RC(upload(enc, enc->wemb, *w));
+    RC(upload(enc, enc->pemb, *p));
+    RC(upload(enc, enc->temb, *t));
+    RC(upload(enc, enc->emb_g, *g));
+    RC(upload(enc, enc->emb_b, *b));
     if (E != D) {
       GETW(pw, "embeddings_project.weight", (size_t)D * E);
       GETW(pb, "embeddings_project.bias", D);
       RC(up_linear(enc, enc->eproj, enc->eproj_h, enc->eproj_b, *pw, *pb));
     }
   }
-  enc->layers.assign(d.depth, EncLayer{});
+  enc->layers.clear();
+  enc->layers.resize(d.depth);
   for (int i = 0; i < d.depth; ++i) {
     const std::string pre = "encoder.layer." + std::to_string(i) + ".";
     EncLayer& L = enc->layers[i];
@@ -241,19 +176,19 @@ int finalize_text(mmpfn_enc* enc) {
     RC(up_linear(enc, L.proj, L.proj_h, L.proj_b, *ow, *ob));
     RC(up_linear(enc, L.fc1, L.fc1_h, L.fc1_b, *iw, *ib));
     RC(up_linear(enc, L.fc2, L.fc2_h, L.fc2_b, *o2w, *o2b));
-    RC(upload(enc, L.ln1g, *l1g, false));
-    RC(upload(enc, L.ln1b, *l1b, false));
-    RC(upload(enc, L.ln2g, *l2g, false));
-    RC(upload(enc, L.ln2b, *l2b, false));
+    RC(upload(enc, L.ln1g, *l1g));
+    RC(upload(enc, L.ln1b, *l1b));
+    RC(upload(enc, L.ln2g, *l2g));
+    RC(upload(enc, L.ln2b, *l2b));
   }
   return MMPFN_OK;
 }
 
-inline const void* Wsel(const Buf& f, const Buf& h, int prec) { return prec == PREC_BF16 ? h.p : f.p; }
+inline const void* Wsel(const DevBuf& f, const DevBuf& h, int prec) { return prec == PREC_BF16 ? h.p : f.p; }
 
 // C = A . W^T + bias, epilogue per mode; fp32 parity mode: the generic fp32-MFMA GEMM (gemm.hip)
 // into Y, then the residual / store step
-int linear(mmpfn_enc* enc, int prec, const void* A, const Buf& Wf, const Buf& Wh, const Buf& bias, int M, int N,
+int linear(mmpfn_enc* enc, int prec, const void* A, const DevBuf& Wf, const DevBuf& Wh, const DevBuf& bias, int M, int N,
            int K, int epi, int act, void* C, const float* gamma, float* Y) {
   if (M <= 0) return MMPFN_OK;
   if (prec == PREC_BF16) {
@@ -302,7 +237,7 @@ int pos_for(mmpfn_enc* enc, int gh, int gw, const float** out) {
   auto key = std::make_pair(gh, gw);
   auto it = enc->pos_cache.find(key);
   if (it == enc->pos_cache.end()) {
-    Buf b;
+    DevBuf b;
     RC(ensure(enc, b, (size_t)(1 + gh * gw) * D * 4));
     // torch upsample_bicubic2d source scale: 1 / scale_factor (double -> float) when the reference
     // passes scale factors ((g + offset) / M), else input / output
@@ -315,7 +250,7 @@ int pos_for(mmpfn_enc* enc, int gh, int gw, const float** out) {
       sw = (float)M / (float)gw;
     }
     HIPCHK(launch_pos_interp((const float*)enc->pos.p, M, D, gh, gw, sh, sw, (float*)b.p, enc->stream));
-    it = enc->pos_cache.emplace(key, b).first;
+    it = enc->pos_cache.emplace(key, std::move(b)).first;
   }
   *out = (const float*)it->second.p;
   return MMPFN_OK;
@@ -379,20 +314,6 @@ mmpfn_enc* mmpfn_enc_create(int device, void* hip_stream) {
 void mmpfn_enc_destroy(mmpfn_enc* enc) {
   if (!enc) return;
   (void)hipSetDevice(enc->device);
-  auto freeb = [](Buf& b) {
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-  };
-  for (auto& L : enc->layers)
-    for (Buf* b : {&L.ln1g, &L.ln1b, &L.ln2g, &L.ln2b, &L.ls1, &L.ls2, &L.qkv, &L.qkv_h, &L.qkv_b, &L.proj,
-                   &L.proj_h, &L.proj_b, &L.fc1, &L.fc1_h, &L.fc1_b, &L.fc2, &L.fc2_h, &L.fc2_b})
-      freeb(*b);
-  for (auto& kv : enc->pos_cache) freeb(kv.second);
-  for (Buf* b : {&enc->pe_w, &enc->pe_wh, &enc->pe_b, &enc->cls_tok, &enc->pos, &enc->norm_g, &enc->norm_b,
-                 &enc->wemb, &enc->pemb, &enc->temb, &enc->emb_g, &enc->emb_b, &enc->eproj, &enc->eproj_h,
-                 &enc->eproj_b, &enc->X, &enc->A, &enc->QKV, &enc->O, &enc->Hh, &enc->Y, &enc->Xc, &enc->Ac,
-                 &enc->Oc, &enc->Hc, &enc->Yc, &enc->kb, &enc->flag, &enc->P0})
-    freeb(*b);
   delete enc;
 }
 

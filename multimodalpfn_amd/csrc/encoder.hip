@@ -605,8 +605,9 @@ hipError_t launch_encode_stats(const float* x, int S, int F, int N, int G, int f
 hipError_t launch_assemble(const float* x, int S, int F, int G, int fpg, int nf, const SlotParams* slots,
                            const float* w_enc, const float* posemb, const float* tok, int C, const float* y, int N,
                            const float* uniq, int U, const float* yw, const float* yb, const float* ymean, void* X,
-                           bool half, int E, int* flag, hipStream_t st) {
-  if (S <= 0 || G < 0 || C < 0 || U < 0 || N < 0 || N > S) return hipErrorInvalidValue;
+                           DType x_t, int E, int* flag, hipStream_t st) {
+  if (S <= 0 || G < 0 || C < 0 || U < 0 || N < 0 || N > S || x_t == DType::BF16) return hipErrorInvalidValue;
+  const bool half = x_t == DType::F16;
   if ((G > 0 && (!x || !slots || fpg <= 0 || fpg > 8 || nf > 8 || nf < fpg)) || (C > 0 && !tok) || (N > 0 && !y))
     return hipErrorInvalidValue;
   if (E > EMB_EMAX || E % (half ? 8 : 4) != 0 || (int64_t)(G + C + 1) * S >= INT32_MAX / 2) return hipErrorInvalidValue;
@@ -645,13 +646,14 @@ hipError_t launch_decoder(const float* X, int Q, const float* w1t, const float* 
   return hipGetLastError();
 }
 
-hipError_t launch_decoder_mfma(const void* X, bool x_f16, int Q, const void* W1, const float* b1, int Fh, const void* W2p,
+hipError_t launch_decoder_mfma(const void* X, DType x_t, int Q, const void* W1, const float* b1, int Fh, const void* W2p,
                                const float* b2, int n_out, float* out, int E, hipStream_t st, int M, int64_t xm,
                                int64_t om) {
   if (Q <= 0 || M <= 0) return hipSuccess;
-  if (E % 32 != 0 || E > 256 || Fh % 128 != 0 || n_out > 16 || n_out <= 0) return hipErrorInvalidValue;
+  if (E % 32 != 0 || E > 256 || Fh % 128 != 0 || n_out > 16 || n_out <= 0 || x_t == DType::BF16)
+    return hipErrorInvalidValue;
   const dim3 grid((unsigned)((Q + 15) / 16), (unsigned)M);
-  if (x_f16)
+  if (x_t == DType::F16)
     hipLaunchKernelGGL((dec_mfma_kernel<f16>), grid, dim3(256), 0, st, (const f16*)X, Q, xm, W1, b1, Fh, W2p, b2, n_out,
                        out, om, E);
   else

@@ -342,10 +342,10 @@ hipError_t launch_fr(void* X, const void* pk, int S, int T, int M, float eps, hi
 }  // namespace
 
 hipError_t launch_feat_rows(void* X, const void* pack, int S, int T, int M, int E, int H, float eps, hipStream_t st,
-                            bool f16) {
+                            DType x_t) {
   if (S <= 0 || M <= 0) return hipSuccess;
-  if (E != FR_E || H != FR_H || T < 1 || T > 64) return hipErrorInvalidValue;
-  return f16 ? launch_fr<true>(X, pack, S, T, M, eps, st) : launch_fr<false>(X, pack, S, T, M, eps, st);
+  if (E != FR_E || H != FR_H || T < 1 || T > 64 || x_t == DType::BF16) return hipErrorInvalidValue;
+  return x_t == DType::F16 ? launch_fr<true>(X, pack, S, T, M, eps, st) : launch_fr<false>(X, pack, S, T, M, eps, st);
 }
 
 }  // namespace mmpfn

@@ -389,17 +389,6 @@ hipError_t launch_t(const GemmArgs& a, int groups, hipStream_t st) {
   return hipGetLastError();
 }
 
-template <int MODE, bool AF32, bool OF32>
-hipError_t launch_e(const GemmArgs& a, int epi, int groups, hipStream_t st) {
-  switch (epi) {
-    case EPI_STORE: return launch_t<MODE, AF32, OF32, EPI_STORE>(a, groups, st);
-    case EPI_ITEM_QKV: return launch_t<MODE, AF32, OF32, EPI_ITEM_QKV>(a, groups, st);
-    case EPI_RES_LN: return launch_t<MODE, AF32, true, EPI_RES_LN>(a, groups, st);
-    case EPI_GLU: return launch_t<MODE, AF32, OF32, EPI_GLU>(a, groups, st);
-    case EPI_REMAP: return launch_t<MODE, AF32, OF32, EPI_REMAP>(a, groups, st);
-  }
-  return hipErrorInvalidValue;
-}
 
 // ---------------------------------------------------------------- large-tile GLU GEMM (bf16)
 // The MGM head bank (transformer.py:33-60): C[M][N/2] = GLU(A[M][K] . W[N][K]^T + bias), N = heads x
@@ -650,26 +639,44 @@ hipError_t launch_gemm(const GemmArgs& a, int prec, int epi, bool a_f32, bool ou
                        hipStream_t st) {
   if (a.M <= 0) return hipSuccess;
   if (a.N % BN != 0) return hipErrorInvalidValue;
+  // only the (mode, epilogue, A / C type) combinations the engine launches are instantiated (kernels.h)
   if (prec == PREC_F32_MFMA) {
     if (!a_f32 || !out_f32) return hipErrorInvalidValue;
     if (a.K % 32 != 0) return hipErrorInvalidValue;
-    return launch_e<0, true, true>(a, epi, groups, st);
+    switch (epi) {
+      case EPI_STORE: return launch_t<0, true, true, EPI_STORE>(a, groups, st);
+      case EPI_ITEM_QKV: return launch_t<0, true, true, EPI_ITEM_QKV>(a, groups, st);
+      case EPI_RES_LN: return launch_t<0, true, true, EPI_RES_LN>(a, groups, st);
+      case EPI_GLU: return launch_t<0, true, true, EPI_GLU>(a, groups, st);
+      case EPI_REMAP: return launch_t<0, true, true, EPI_REMAP>(a, groups, st);
+    }
+    return hipErrorInvalidValue;
   }
   if (a.K % 64 != 0) return hipErrorInvalidValue;
   if (prec == PREC_F32) {  // x3: fp32 A split while staged, W given as hi | lo planes (w_lo_off)
     if (!a_f32 || !out_f32 || a.w_lo_off <= 0) return hipErrorInvalidValue;
-    return launch_e<2, true, true>(a, epi, groups, st);
+    switch (epi) {
+      case EPI_STORE: return launch_t<2, true, true, EPI_STORE>(a, groups, st);
+      case EPI_GLU: return launch_t<2, true, true, EPI_GLU>(a, groups, st);
+      case EPI_REMAP: return launch_t<2, true, true, EPI_REMAP>(a, groups, st);
+    }
+    return hipErrorInvalidValue;
   }
-  if (a_f32) {
-    return out_f32 ? launch_e<1, true, true>(a, epi, groups, st) : launch_e<1, true, false>(a, epi, groups, st);
-  }
-  return out_f32 ? launch_e<1, false, true>(a, epi, groups, st) : launch_e<1, false, false>(a, epi, groups, st);
+  if (prec != PREC_BF16) return hipErrorInvalidValue;
+  if (epi == EPI_STORE && !a_f32 && !out_f32) return launch_t<1, false, false, EPI_STORE>(a, groups, st);
+  if (epi == EPI_GLU && !a_f32 && !out_f32) return launch_t<1, false, false, EPI_GLU>(a, groups, st);
+  if (epi == EPI_REMAP && !a_f32 && out_f32) return launch_t<1, false, true, EPI_REMAP>(a, groups, st);
+  if (epi == EPI_ITEM_QKV && a_f32 && !out_f32) return launch_t<1, true, false, EPI_ITEM_QKV>(a, groups, st);
+  if (epi == EPI_RES_LN && !a_f32 && out_f32) return launch_t<1, false, true, EPI_RES_LN>(a, groups, st);
+  return hipErrorInvalidValue;
 }
 
-hipError_t launch_gemm_remap_big(const void* A, int64_t lda, const void* W, const float* bias, void* C, bool c_bf16,
-                                 int M, int K, int nheads, int n_mod, int E, hipStream_t st, bool f16) {
+hipError_t launch_gemm_remap_big(const void* A, int64_t lda, const void* W, const float* bias, void* C, DType c_t,
+                                 int M, int K, int nheads, int n_mod, int E, hipStream_t st, DType t) {
   if (M <= 0) return hipSuccess;
   if (E != GR_N || K % GB_K != 0 || K <= 0 || nheads <= 0 || n_mod <= 0) return hipErrorInvalidValue;
+  if (t == DType::F32 || (c_t != DType::F32 && c_t != t)) return hipErrorInvalidValue;
+  const bool f16 = t == DType::F16, c_bf16 = c_t != DType::F32;  // c_bf16: C in the operands' 16-bit type
   const int mtiles = (M + GR_M - 1) / GR_M;
   const int64_t nb = (int64_t)mtiles * nheads;
   const int lds = GB_NST * GB_STAGE;
@@ -691,9 +698,10 @@ hipError_t launch_gemm_remap_big(const void* A, int64_t lda, const void* W, cons
 }
 
 hipError_t launch_gemm_glu_big(const void* A, const void* W, const float* bias, void* C, int M, int N, int K,
-                               hipStream_t st, bool f16) {
+                               hipStream_t st, DType t) {
   if (M <= 0) return hipSuccess;
-  if (N % GB_N != 0 || K % GB_K != 0 || K <= 0) return hipErrorInvalidValue;
+  if (N % GB_N != 0 || K % GB_K != 0 || K <= 0 || t == DType::F32) return hipErrorInvalidValue;
+  const bool f16 = t == DType::F16;
   const int mtiles = (M + GB_M - 1) / GB_M;
   const int64_t nb = (int64_t)mtiles * (N / GB_N);
   const int lds = GB_NST * GB_STAGE;  // 144 KB

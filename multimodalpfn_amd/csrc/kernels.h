@@ -36,6 +36,9 @@ inline int f8_of(int p) {
 inline bool prec_ok(int p) { return p >= PREC_F32 && p <= PREC_F16_F8E5; }
 inline bool prec16(int p) { return p == PREC_BF16 || p == PREC_F16; }  // a 16-bit performance mode (base)
 
+// element type of a launcher's operand; a combination with no kernel returns hipErrorInvalidValue
+enum class DType : int { F32, BF16, F16 };
+
 enum Epi : int {
   EPI_STORE = 0,      // C[row] = act(acc + bias)
   EPI_ITEM_QKV = 1,   // scatter to attention Q / K / V^T layouts: row m -> (b = m / a_rdiv, pos = a_roff + m % a_rdiv)
@@ -76,56 +79,61 @@ struct GemmArgs {
 };
 
 // Launch C = A . W^T with the given epilogue.  `a_f32` says whether A is stored
-// as fp32 (otherwise bf16); `out_f32` likewise for C / scatter targets.
+// as fp32 (otherwise bf16); `out_f32` likewise for C / scatter targets.  Instantiated: PREC_F32_MFMA every
+// epilogue; PREC_F32 STORE / GLU / REMAP (the mixers; the layers run rowgemm3.hip), both fp32 in and out; PREC_BF16
+// STORE and GLU (bf16 in and out), REMAP (bf16 in, fp32 out), ITEM_QKV (fp32 in, bf16 out), RES_LN (bf16 in, fp32
+// out).  Anything else: hipErrorInvalidValue.
 hipError_t launch_gemm(const GemmArgs& a, int prec, int epi, bool a_f32, bool out_f32, int groups,
                        hipStream_t st);
 
-// MGM head bank, bf16 (fp16 with f16: A, W and C fp16): C[M][N/2] = GLU(A[M][K] . W^T + bias) with W rows GLU-interleaved in 16-row
+// MGM head bank, bf16 or fp16 (t: A, W and C): C[M][N/2] = GLU(A[M][K] . W^T + bias) with W rows GLU-interleaved in 16-row
 // blocks (capi.cpp); large-tile, XCD-ordered (gemm.hip gemm_glu_big_kernel); N % 256 == 0, K % 64 == 0
 // MGM per-head down-projection (bf16, E = 192): C[(r / n_mod) * nheads n_mod + z n_mod + r % n_mod][E] =
-// A[r][z K .. z K + K) (row stride lda) . W[z][E][K]^T + bias[z][E]; C fp32 or bf16 (c_bf16); with f16, A and W
-// fp16 and C fp32 or fp16 (c_bf16)
-hipError_t launch_gemm_remap_big(const void* A, int64_t lda, const void* W, const float* bias, void* C, bool c_bf16,
-                                 int M, int K, int nheads, int n_mod, int E, hipStream_t st, bool f16 = false);
+// A[r][z K .. z K + K) (row stride lda) . W[z][E][K]^T + bias[z][E]; A and W in t (bf16 or fp16), C in c_t: fp32 or t
+hipError_t launch_gemm_remap_big(const void* A, int64_t lda, const void* W, const float* bias, void* C, DType c_t,
+                                 int M, int K, int nheads, int n_mod, int E, hipStream_t st, DType t = DType::BF16);
 hipError_t launch_gemm_glu_big(const void* A, const void* W, const float* bias, void* C, int M, int N, int K,
-                               hipStream_t st, bool f16 = false);
+                               hipStream_t st, DType t = DType::BF16);
 
-// fused MLP sublayer: X <- LN(X + GELU(X W1^T) W2^T), W1 [Fh][E], W2 [E][Fh] in compute dtype
+// fused MLP sublayer of the fp32 modes: X <- LN(X + GELU(X W1^T) W2^T); PREC_F32_MFMA: W1 [Fh][E], W2 [E][Fh]
+// fp32; PREC_F32: W1 natural and W2 in the pack_mlp2_perm order, each as bf16 hi | lo planes
 hipError_t launch_mlp_fused(float* X, const void* W1, const void* W2, int64_t M, int E, int Fh, float eps, int prec,
                             hipStream_t st);
 
-// row-resident MLP sublayer (bf16 only, mlp_rows.hip): W1 [Fh][E] bf16, W2 [E][Fh] bf16 in the
+// row-resident MLP sublayer (the 16-bit modes, mlp_rows.hip): W1 [Fh][E] bf16, W2 [E][Fh] bf16 in the
 // permuted hidden order of pack_mlp2_perm (capi.cpp); Fh % 32 == 0, E == 192
 // W1perm: W1 with its K (feature) order permuted to the Y^T lane layout (capi.cpp pack_mlp1_perm);
 // O / Wout non-null: X <- LN(X + O Wout^T) first (the item-attention out-projection, fused)
-// f16 (PREC_F16): X / O fp16, W1 natural, W2 (pack_mlp2_perm) and Wout with f16_row_perm-ordered rows
+// x_t: the state's type, fp32 (bf16 operands) or fp16 (PREC_F16: X / O fp16, W1 natural, W2 (pack_mlp2_perm) and
+// Wout with f16_row_perm-ordered rows)
 hipError_t launch_mlp_rows(void* X, const void* W1perm, const void* W2perm, int64_t M, int E, int Fh, float eps,
-                           hipStream_t st, const void* O = nullptr, const void* Wout = nullptr, bool f16 = false);
+                           hipStream_t st, const void* O = nullptr, const void* Wout = nullptr,
+                           DType x_t = DType::F32);
 
 // row-resident item-attention projections (bf16, K = 192, rowgemm.hip):
 //   QKV: X rows (remap (m/rdiv)*rmul + (m%rdiv)*rmul2 + roff) . W^T, W [N][192] (N = 576 or 192),
 //        scattered to Q [b][h][pos][32], K [b][h][pos][32] (Npad rows), V^T [b][h][32][Npad],
 //        b = m / rdiv, pos = roff + m % rdiv
 //   RES_LN: X <- LN(X + O . W^T), O [M][192] bf16, W [192][192] bf16
-//   f16 (PREC_F16): X fp16, W fp16, Q / K fp16 (V^T stays bf16); RES_LN: O / X fp16, W rows in
-//   f16_row_perm order (weight_pack.h)
+//   x_t: the state's type, fp32 (bf16 W, Q / K; qk_t bf16) or fp16 (PREC_F16: X fp16, W fp16, Q / K in qk_t, fp16
+//   or bf16; V^T stays bf16); RES_LN: O bf16 / X fp32, or both fp16 with W rows in f16_row_perm order (weight_pack.h)
 hipError_t launch_rowgemm_qkv(const void* X, int64_t a_rdiv, int64_t a_rmul, int64_t a_rmul2, int64_t a_roff,
                               const void* W, int M, int N, void* q, void* k, void* vt, int S, int Npad, int H,
-                              hipStream_t st, bool f16 = false, bool qk_bf16 = false);  // qk_bf16: f16 X, bf16 Q / K
+                              hipStream_t st, DType x_t = DType::F32, DType qk_t = DType::BF16);
 // two row sets (train rows: q|k|v, test rows: q) of the same token columns in ONE launch,
 // rows m -> memory row (m / rdiv) * a_rmul + m % rdiv + roff of each set
 hipError_t launch_rowgemm_qkv_pair(const void* X, int64_t rdiv1, int64_t roff1, const void* W1, int M1, int N1,
                                    int64_t rdiv2, int64_t roff2, const void* W2, int M2, int N2, int64_t a_rmul,
                                    void* q, void* k, void* vt, int S, int Npad, int H, hipStream_t st,
-                                   bool f16 = false, bool qk_bf16 = false);
-// C = (ln ? LayerNorm(A) : A) . W^T + bias: A fp32, bf16 or fp16 (a_f16) [M][192], W [N][192] bf16, C bf16 [M][N], N % 64 == 0;
+                                   DType x_t = DType::F32, DType qk_t = DType::BF16);
+// C = (ln ? LayerNorm(A) : A) . W^T + bias: A fp32, bf16 or fp16 (a_t) [M][192], W [N][192] bf16, C bf16 [M][N], N % 64 == 0;
 // with CT: outputs [vt_from, N) transposed per group of Mk rows into CT [M / Mk][N - vt_from][Mk] (Mk % 32 == 0),
 // C then [M][vt_from]
-hipError_t launch_rowgemm_ln_store(const void* A, bool a_bf16, const void* W, const float* bias, void* C, int64_t M,
+hipError_t launch_rowgemm_ln_store(const void* A, DType a_t, const void* W, const float* bias, void* C, int64_t M,
                                    int N, float eps, bool ln, hipStream_t st, void* CT = nullptr, int vt_from = -1,
-                                   int Mk = 0, bool a_f16 = false);
+                                   int Mk = 0);
 hipError_t launch_rowgemm_resln(const void* O, const void* W, int64_t M, void* X, float eps, hipStream_t st,
-                                bool f16 = false);
+                                DType x_t = DType::F32);
 
 // parity-mode (x3 split-bf16) row-resident projections of width 192 (rowgemm3.hip), fp32 in and out:
 // W = the hi plane [N][192] of capi.cpp upsplit, its lo plane at W + w_lo elements.
@@ -143,21 +151,16 @@ hipError_t launch_proj3_qkv(const Proj3Set* sets, int nset, void* q, void* k, vo
 hipError_t launch_proj3_resln(const float* O, const void* W, int64_t w_lo, int64_t M, float* X, float eps,
                               hipStream_t st);
 
-// row-resident attention-between-features sublayer (bf16 only, featrow.hip): one wave per
+// row-resident attention-between-features sublayer (the 16-bit modes, featrow.hip): one wave per
 // table row, T <= 64 tokens; `pack` (capi.cpp pack_feat_rows) = LDS images with 416-B rows:
 // per head [96][FEAT_IMG_STRIDE] (Wq rows permuted & scaled by log2(e)/sqrt(32) | Wk rows
 // permuted | Wv), then the out-projection [192][FEAT_IMG_STRIDE] with permuted head columns
 // (FEAT_IMG_STRIDE, FEAT_PACK_LAYER: weight_pack.h)
 // X holds M members [M][T][S][E]; one launch covers the M*S rows
-// f16: PREC_F16 -- X fp16, pack the fp16 images with the out-projection rows permuted (pack_feat_rows res_perm)
+// x_t: the state's type, fp32 (bf16 images) or fp16 (PREC_F16: the fp16 images with the out-projection rows permuted,
+// pack_feat_rows res_perm)
 hipError_t launch_feat_rows(void* X, const void* pack, int S, int T, int M, int E, int H, float eps, hipStream_t st,
-                            bool f16 = false);
-
-// fused attention-between-features sublayer (bf16 only): X <- LN(X + MHA_feat(X)) per row,
-// wqkv [3*H*32][E] bf16, wout [E][H*32] bf16; rows per block = feat_block_rows(T) (0: unsupported T)
-int feat_block_rows(int T);
-hipError_t launch_feat_block(float* X, const void* wqkv, const void* wout, int S, int T, int E, int H, float eps,
-                             hipStream_t st);
+                            DType x_t = DType::F32);
 
 // ---- attention -------------------------------------------------------------------
 // generic MFMA attention over a batch (blockIdx.z) of independent sequences:
@@ -203,16 +206,29 @@ hipError_t launch_attn_pipe(const Attn2Args& a, hipStream_t st);
 //   cache; then na = 0 and kvb = 0)
 //   f8 != 0: P.V and the row sums on block-scaled fp8 MFMA with vt8 = V^T in e4m3 (launch_vt_fp8), P in
 //   e4m3 (1) or e5m2 (2); vt (bf16) still serves the exact re-run path
-hipError_t launch_attn_layer(const void* q, const void* k, const void* vt, void* out, int S, int T, int H, int Npad,
-                             int nk, int a0, int na, int b0, int nb, int kvb, hipStream_t st, int64_t kv_bstride = 0,
-                             bool q_prescaled = false,  // Q already scaled by log2(e)/sqrt(32)
-                             const void* vt8 = nullptr, int f8 = 0, bool qk_f16 = false, bool o_f16 = false);
+//   qk_t: Q and K bf16, or fp16 (S on the f16 MFMA; then o_t is fp16 too: the fp16 tap); o_t: O bf16 or fp16
+//   (PREC_F16's forward: bf16 Q / K, fp16 O); V^T stays bf16
+struct AttnLayerArgs {
+  const void* q;
+  const void* k;
+  const void* vt;
+  void* out;
+  int S, T, H, Npad, nk;
+  int a0, na;                  // own-head query rows
+  int b0, nb, kvb;             // shared-KV query rows against kv head kvb
+  int64_t kv_bstride = 0;      // 0: no cache stride (K / V^T hold every head)
+  bool q_prescaled = false;    // Q already scaled by log2(e)/sqrt(32)
+  const void* vt8 = nullptr;
+  int f8 = 0;
+  DType qk_t = DType::BF16, o_t = DType::BF16;
+};
+hipError_t launch_attn_layer(const AttnLayerArgs& a, hipStream_t st);
 // bf16 -> e4m3 (saturating) of n elements (n % 8 == 0): the F8 attention's V^T operand
 hipError_t launch_vt_fp8(const void* vt, void* vt8, int64_t n, hipStream_t st);
-// parity mode (PREC_F32) of launch_attn_layer on fp32 Q / K / V^T (split bf16 three-product MFMAs), fp32 O
+// parity mode (PREC_F32) of launch_attn_layer on fp32 Q / K / V^T (split bf16 three-product MFMAs), fp32 O; the
+// prescale, fp8 and element-type fields do not apply
 int set_x3_cheap_min_keys(int n, int form);  // previous value; mmpfn_set_parity_attention_min_keys
-hipError_t launch_attn_item3(const void* q, const void* k, const void* vt, void* out, int S, int T, int H, int Npad,
-                             int nk, int a0, int na, int b0, int nb, int kvb, hipStream_t st, int64_t kv_bstride = 0);
+hipError_t launch_attn_item3(const AttnLayerArgs& a, hipStream_t st);
 // item attention: queries s in [s0, s0+nq), keys [0, nk); kv_head_fixed >= 0 forces that KV head
 hipError_t launch_attn_item(const void* q, const void* k, const void* vt, void* out, int S, int T, int H,
                             int Npad, int s0, int nq, int nk, int kv_head_fixed, int prec, hipStream_t st,
@@ -230,12 +246,12 @@ struct SlotParams {  // per (group, slot): how to transform raw column -> model 
 // ymean[0] over y[0, ny), one launch
 hipError_t launch_encode_stats(const float* x /*[S][F]*/, int S, int F, int N, int G, int fpg, float sigma,
                                SlotParams* slots, const float* y, int ny, float* ymean, hipStream_t st);
-// the member's input state X [T][S][E] (T = G + C + 1), fp32 or fp16 (f16): x tokens from the slots, mixer
+// the member's input state X [T][S][E] (T = G + C + 1), fp32 or fp16 (x_t): x tokens from the slots, mixer
 // tokens + positional rows, the label token (labels y[0, N); rows >= N are test rows); NaN -> flag bits 1 / 2
 hipError_t launch_assemble(const float* x, int S, int F, int G, int fpg, int nf, const SlotParams* slots,
                            const float* w_enc /*[E][2nf]*/, const float* posemb /*[G+C][E]*/,
                            const float* tok /*[S][C][E]*/, int C, const float* y, int N, const float* uniq, int U,
-                           const float* yw /*[E][2]*/, const float* yb, const float* ymean, void* X, bool f16, int E,
+                           const float* yw /*[E][2]*/, const float* yb, const float* ymean, void* X, DType x_t, int E,
                            int* flag, hipStream_t st);
 hipError_t launch_pos_emb(const float* rnd /*[n][E/4]*/, int n, const float* w /*[E][E/4]*/,
                           const float* b, float* out /*[n][E]*/, int E, hipStream_t st);
@@ -244,9 +260,9 @@ hipError_t launch_decoder(const float* X /*[Q][E]*/, int Q, const float* w1t /*[
                           const float* w2, const float* b2, int n_out, float* out, int E, hipStream_t st, int M,
                           int64_t xm, int64_t om, float* scratch);
 
-// the 16-bit modes' decoder on MFMA: X fp32 (bf16 operands) or fp16 (x_f16, fp16 operands); W1 [Fh][E] and W2p
+// the 16-bit modes' decoder on MFMA: X (x_t) fp32 (bf16 operands) or fp16 (fp16 operands); W1 [Fh][E] and W2p
 // [16][Fh] (pack_mlp2_perm order, rows >= n_out zero) in the operand type; Fh % 128 == 0, n_out <= 16
-hipError_t launch_decoder_mfma(const void* X, bool x_f16, int Q, const void* W1, const float* b1, int Fh, const void* W2p,
+hipError_t launch_decoder_mfma(const void* X, DType x_t, int Q, const void* W1, const float* b1, int Fh, const void* W2p,
                                const float* b2, int n_out, float* out, int E, hipStream_t st, int M, int64_t xm,
                                int64_t om);
 // PREC_F16 state conversions: nb blocks of per_block elements (per_block % 4 == 0) at the given block
@@ -262,11 +278,11 @@ hipError_t launch_aggregate(const float* logits /*[M][Q][n_out]*/, int M, int Q,
                             const float* class_weights /*[n_cls] or null*/, float* probs, hipStream_t st);
 
 // ---- mixer helpers -----------------------------------------------------------------
-hipError_t launch_layernorm_rows(const float* in, int64_t rows, int dim, float eps, void* out, bool out_f32,
-                                 const float* gamma, const float* beta, hipStream_t st, bool out_f16 = false);
-hipError_t launch_cap_attention(const float* qp /*[cap][E]*/, const void* kv /*[S][M][2E]*/, bool kv_f32,
-                                void* out /*[S][cap][E] fp32, or bf16 (out_bf16)*/, bool out_bf16, int S, int M, int cap,
-                                int E, hipStream_t st);
+hipError_t launch_layernorm_rows(const float* in, int64_t rows, int dim, float eps, void* out, DType out_t,
+                                 const float* gamma, const float* beta, hipStream_t st);
+// kv and out both fp32 (the fp32 modes) or both bf16
+hipError_t launch_cap_attention(const float* qp /*[cap][E]*/, const void* kv /*[S][M][2E]*/, DType kv_t,
+                                void* out /*[S][cap][E]*/, DType out_t, int S, int M, int cap, int E, hipStream_t st);
 // CAP core on MFMA (bf16; head dim 8, 24 heads = cap queries, M % 32 == 0, M <= 128): K [S*M][E], V^T [S][E][M]
 // bf16 (launch_rowgemm_ln_store's transposed form), O bf16 [S][cap][E]; hipErrorNotSupported for other shapes
 hipError_t launch_cap_attention_mfma(const float* qp, const void* K, const void* VT, void* out, int S, int M, int cap,

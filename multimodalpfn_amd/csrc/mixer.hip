@@ -336,8 +336,8 @@ __global__ void scale_tokens_kernel(float* __restrict__ tok, const float* __rest
 
 }  // namespace
 
-hipError_t launch_layernorm_rows(const float* in, int64_t rows, int dim, float eps, void* out, bool out_f32,
-                                 const float* gamma, const float* beta, hipStream_t st, bool out_f16) {
+hipError_t launch_layernorm_rows(const float* in, int64_t rows, int dim, float eps, void* out, DType out_t,
+                                 const float* gamma, const float* beta, hipStream_t st) {
   if (rows <= 0) return hipSuccess;
   dim3 grid((rows + 3) / 4);
   const int v4 = dim % 4 ? 0 : (dim / 4 + 63) / 64;  // float4 registers per lane
@@ -353,8 +353,8 @@ hipError_t launch_layernorm_rows(const float* in, int64_t rows, int dim, float e
     else if (v4 == 4) go(tag, std::integral_constant<int, 4>{});
     else go(tag, std::integral_constant<int, 0>{});
   };
-  if (out_f32) pick(float{});
-  else if (out_f16) pick(_Float16{});
+  if (out_t == DType::F32) pick(float{});
+  else if (out_t == DType::F16) pick(_Float16{});
   else pick(bf16{});
   return hipGetLastError();
 }
@@ -384,14 +384,13 @@ hipError_t launch_cap_t(const float* qp, const TK* kv, TO* out, int S, int M, in
   return hipGetLastError();
 }
 
-hipError_t launch_cap_attention(const float* qp, const void* kv, bool kv_f32, void* out, bool out_bf16, int S, int M,
+hipError_t launch_cap_attention(const float* qp, const void* kv, DType kv_t, void* out, DType out_t, int S, int M,
                                 int cap, int E, hipStream_t st) {
   if (S <= 0) return hipSuccess;
   if (E % cap != 0) return hipErrorInvalidValue;
-  if (kv_f32) return out_bf16 ? launch_cap_t(qp, (const float*)kv, (bf16*)out, S, M, cap, E, st)
-                              : launch_cap_t(qp, (const float*)kv, (float*)out, S, M, cap, E, st);
-  return out_bf16 ? launch_cap_t(qp, (const bf16*)kv, (bf16*)out, S, M, cap, E, st)
-                  : launch_cap_t(qp, (const bf16*)kv, (float*)out, S, M, cap, E, st);
+  if (kv_t == DType::F32 && out_t == DType::F32) return launch_cap_t(qp, (const float*)kv, (float*)out, S, M, cap, E, st);
+  if (kv_t == DType::BF16 && out_t == DType::BF16) return launch_cap_t(qp, (const bf16*)kv, (bf16*)out, S, M, cap, E, st);
+  return hipErrorInvalidValue;
 }
 
 hipError_t launch_cap_attention_mfma(const float* qp, const void* K, const void* VT, void* out, int S, int M, int cap,

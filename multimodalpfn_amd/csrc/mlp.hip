@@ -369,18 +369,16 @@ hipError_t launch_mlp_fused(float* X, const void* W1, const void* W2, int64_t M,
   if (M <= 0) return hipSuccess;
   if (E != ME || Fh % ME != 0) return hipErrorInvalidValue;
   dim3 grid((M + MBM - 1) / MBM);
-  static std::atomic<uint64_t> opted1{0}, opted0{0};  // > 64 KiB dynamic LDS needs an explicit opt-in
-  hipError_t e = lds_optin(opted1, (const void*)mlp_fused_kernel<1>, MlpLds<1>::BYTES);
-  if (e != hipSuccess) return e;
-  e = lds_optin(opted0, (const void*)mlp_fused_kernel<0>, MlpLds<0>::BYTES);
-  if (e != hipSuccess) return e;
-  if (prec == PREC_BF16)
-    hipLaunchKernelGGL(mlp_fused_kernel<1>, grid, dim3(256), MlpLds<1>::BYTES, st, X, W1, W2, (int)M, Fh, eps);
-  else if (prec == PREC_F32)  // W1 natural, W2 in the pack_mlp2_perm order, each as hi | lo planes
+  if (prec == PREC_F32) {  // W1 natural, W2 in the pack_mlp2_perm order, each as hi | lo planes
     hipLaunchKernelGGL(mlp_x3_kernel, dim3((unsigned)((M + 63) / 64)), dim3(256), 0, st, X, (const bf16*)W1,
                        (const bf16*)W2, (int)M, Fh, eps);
-  else
-    hipLaunchKernelGGL(mlp_fused_kernel<0>, grid, dim3(256), MlpLds<0>::BYTES, st, X, W1, W2, (int)M, Fh, eps);
+    return hipGetLastError();
+  }
+  if (prec != PREC_F32_MFMA) return hipErrorInvalidValue;  // the 16-bit modes run launch_mlp_rows
+  static std::atomic<uint64_t> opted0{0};  // > 64 KiB dynamic LDS needs an explicit opt-in
+  const hipError_t e = lds_optin(opted0, (const void*)mlp_fused_kernel<0>, MlpLds<0>::BYTES);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(mlp_fused_kernel<0>, grid, dim3(256), MlpLds<0>::BYTES, st, X, W1, W2, (int)M, Fh, eps);
   return hipGetLastError();
 }
 

@@ -584,10 +584,10 @@ hipError_t launch_cap_tail(const void* O, const void* Wout, const void* W1perm, 
 }
 
 hipError_t launch_mlp_rows(void* X, const void* W1perm, const void* W2perm, int64_t M, int E, int Fh, float eps,
-                           hipStream_t st, const void* O, const void* Wout, bool f16) {
+                           hipStream_t st, const void* O, const void* Wout, DType x_t) {
   if (M <= 0) return hipSuccess;
-  if (E != RE || Fh % RHC != 0) return hipErrorInvalidValue;
-  return f16 ? launch_mr<true>(X, W1perm, W2perm, M, Fh, eps, st, O, Wout)
+  if (E != RE || Fh % RHC != 0 || x_t == DType::BF16) return hipErrorInvalidValue;
+  return x_t == DType::F16 ? launch_mr<true>(X, W1perm, W2perm, M, Fh, eps, st, O, Wout)
              : launch_mr<false>(X, W1perm, W2perm, M, Fh, eps, st, O, Wout);
 }
 

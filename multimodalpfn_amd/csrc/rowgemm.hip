@@ -561,14 +561,20 @@ hipError_t qkv_rowset(const void* X, int64_t a_rdiv, int64_t a_rmul, int64_t a_r
   nblk = (int64_t)tiles * (M / a_rdiv);
   return hipSuccess;
 }
+// fp32 state: bf16 Q / K; fp16 state: fp16 or bf16 Q / K
+bool qkv_types_ok(DType x_t, DType qk_t) {
+  return x_t == DType::F32 ? qk_t == DType::BF16 : x_t == DType::F16 && qk_t != DType::F32;
+}
 }  // namespace
 
 hipError_t launch_rowgemm_qkv(const void* X, int64_t a_rdiv, int64_t a_rmul, int64_t a_rmul2, int64_t a_roff,
                               const void* W, int M, int N, void* q, void* k, void* vt, int S, int Npad, int H,
-                              hipStream_t st, bool f16, bool qk_bf16) {
+                              hipStream_t st, DType x_t, DType qk_t) {
   RgArgs a;
   int tiles;
   int64_t nblk;
+  if (!qkv_types_ok(x_t, qk_t)) return hipErrorInvalidValue;
+  const bool f16 = x_t == DType::F16, qk_bf16 = qk_t == DType::BF16;
   hipError_t e = qkv_rowset(X, a_rdiv, a_rmul, a_rmul2, a_roff, W, M, N, q, k, vt, S, Npad, H, a, tiles, nblk);
   if (e != hipSuccess || nblk == 0) return e;
   const dim3 g((unsigned)nblk);
@@ -580,11 +586,13 @@ hipError_t launch_rowgemm_qkv(const void* X, int64_t a_rdiv, int64_t a_rmul, int
 
 hipError_t launch_rowgemm_qkv_pair(const void* X, int64_t rdiv1, int64_t roff1, const void* W1, int M1, int N1,
                                    int64_t rdiv2, int64_t roff2, const void* W2, int M2, int N2, int64_t a_rmul,
-                                   void* q, void* k, void* vt, int S, int Npad, int H, hipStream_t st, bool f16,
-                                   bool qk_bf16) {
+                                   void* q, void* k, void* vt, int S, int Npad, int H, hipStream_t st, DType x_t,
+                                   DType qk_t) {
   RgArgs a1, a2;
   int t1, t2;
   int64_t n1, n2;
+  if (!qkv_types_ok(x_t, qk_t)) return hipErrorInvalidValue;
+  const bool f16 = x_t == DType::F16, qk_bf16 = qk_t == DType::BF16;
   hipError_t e = qkv_rowset(X, rdiv1, a_rmul, 1, roff1, W1, M1, N1, q, k, vt, S, Npad, H, a1, t1, n1);
   if (e != hipSuccess) return e;
   e = qkv_rowset(X, rdiv2, a_rmul, 1, roff2, W2, M2, N2, q, k, vt, S, Npad, H, a2, t2, n2);
@@ -598,8 +606,10 @@ hipError_t launch_rowgemm_qkv_pair(const void* X, int64_t rdiv1, int64_t roff1, 
   return hipGetLastError();
 }
 
-hipError_t launch_rowgemm_resln(const void* O, const void* W, int64_t M, void* X, float eps, hipStream_t st, bool f16) {
+hipError_t launch_rowgemm_resln(const void* O, const void* W, int64_t M, void* X, float eps, hipStream_t st, DType x_t) {
   if (M <= 0) return hipSuccess;
+  if (x_t == DType::BF16) return hipErrorInvalidValue;
+  const bool f16 = x_t == DType::F16;
   RgArgs a{};
   a.A = O, a.a_rdiv = 1, a.a_rmul = 1, a.a_rmul2 = 0, a.a_roff = 0;
   a.W = W, a.M = (int)M, a.N = GE, a.X = X, a.eps = eps;
@@ -609,19 +619,18 @@ hipError_t launch_rowgemm_resln(const void* O, const void* W, int64_t M, void* X
   return hipGetLastError();
 }
 
-hipError_t launch_rowgemm_ln_store(const void* A, bool a_bf16, const void* W, const float* bias, void* C, int64_t M,
-                                   int N, float eps, bool ln, hipStream_t st, void* CT, int vt_from, int Mk,
-                                   bool a_f16) {
+hipError_t launch_rowgemm_ln_store(const void* A, DType a_t, const void* W, const float* bias, void* C, int64_t M,
+                                   int N, float eps, bool ln, hipStream_t st, void* CT, int vt_from, int Mk) {
   if (M <= 0) return hipSuccess;
   if (N % QC != 0 || N <= 0 || M > INT32_MAX) return hipErrorInvalidValue;
   if (CT && (vt_from < 0 || vt_from % QC != 0 || vt_from >= N || Mk <= 0 || Mk % 32 != 0 || M % Mk != 0))
     return hipErrorInvalidValue;
   const int ldc = CT ? vt_from : N;
   const dim3 grid((unsigned)((M + GROWS - 1) / GROWS));
-  if (a_f16)
+  if (a_t == DType::F16)
     hipLaunchKernelGGL((rowgemm_ln_store_kernel<_Float16>), grid, dim3(256), 0, st, (const _Float16*)A, (const bf16*)W,
                        bias, (bf16*)C, (int)M, N, eps, ln ? 1 : 0, ldc, (bf16*)CT, CT ? vt_from : -1, CT ? Mk : 1);
-  else if (a_bf16)
+  else if (a_t == DType::BF16)
     hipLaunchKernelGGL((rowgemm_ln_store_kernel<bf16>), grid, dim3(256), 0, st, (const bf16*)A, (const bf16*)W, bias,
                        (bf16*)C, (int)M, N, eps, ln ? 1 : 0, ldc, (bf16*)CT, CT ? vt_from : -1, CT ? Mk : 1);
   else

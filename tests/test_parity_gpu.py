@@ -822,7 +822,7 @@ def test_item_attention_entry_rejects_16bit_and_fp8_codes():
 
 def test_f16_falls_back_to_bf16_on_wide_tables():
     """PREC_F16's layer kernels hold at most 64 tokens per row; wider tables run the bf16 mode.  The
-    forward, the train-KV cache and every sublayer tap apply the same rule (capi.cpp f16_fits), so PREC_F16 equals
+    forward, the train-KV cache and every sublayer tap apply the same rule (capi.cpp decode_prec), so PREC_F16 equals
     PREC_BF16 bitwise there: 140 features = 71 tokens per row.  (The engine is specialised for E = 192 in 6 heads;
     mmpfn_set_model refuses other widths.)"""
     from synth import synth_labels, synth_state_dict, synth_table
