@@ -118,6 +118,18 @@ int mmpfn_mixer_forward(mmpfn_ctx* ctx, const float* image, int S, int n_mod, fl
 int mmpfn_forward(mmpfn_ctx* ctx, const float* x, int S, int F, const float* tokens, int C, const float* y_train,
                   int N, const float* uniq, int U, const float* pos_rand, float* logits, int precision);
 
+/* The last layer of the forward entry points (mmpfn_forward, mmpfn_forward_batch, mmpfn_cache_build,
+ * mmpfn_cache_predict) computes only what the decoder reads: the feature attention of every row at its target token,
+ * then the item attention, out-projection and MLP of the target token's column alone, for its test rows (a cache build: that
+ * column's K / V^T and nothing after).  Every kernel computes a state row from that row's own inputs, so the logits
+ * are bit for bit those of a full last layer.  After such a forward the last layer's state is defined only at the
+ * target token's test rows -- mmpfn_copy_state then returns the rest as earlier sublayers left it.
+ * mmpfn_run_layers always runs full layers, so mmpfn_copy_state after it is the whole state as before; so do the
+ * per-sublayer taps.
+ * mmpfn_set_full_last_layer(ctx, 1) makes the forward entry points of this context run the last layer in full
+ * too (the pruned form's reference and A/B handle); 0, the default, prunes. */
+int mmpfn_set_full_last_layer(mmpfn_ctx* ctx, int on);
+
 /* forward split at its seams (parity taps) */
 int mmpfn_embed(mmpfn_ctx* ctx, const float* x, int S, int F, const float* tokens, int C, const float* y_train, int N,
                 const float* uniq, int U, const float* pos_rand, int precision);
@@ -194,7 +206,9 @@ int mmpfn_item_attention_cached(mmpfn_ctx* ctx, const void* q, const void* k0, c
  *   (multiquery item attention, layer.py:341-358; only_cache_first_head_kv, :362-372) -- and the
  *   train statistics of the x / y encoders and the positional embeddings.  Replaces
  *   InferenceEngineCacheKV.prepare's ens_model.forward(..., single_eval_pos=len(X))
- *   (inference.py:425-436; cache_kv=True, multi_head_attention.py:461-472).
+ *   (inference.py:425-436; cache_kv=True, multi_head_attention.py:461-472).  Of the last layer only the target
+ *   token's column is kept (the pruned last layer above): its other columns' blocks keep their place in the
+ *   layout and in mmpfn_cache_bytes, and are never written or read.
  * mmpfn_cache_predict: Q test rows (x [Q][F], tokens [Q][C][E]) through the layers against the
  *   cache (use_cached_kv, layer.py:344-358), logits [Q][n_out] in the cache's precision.  Replaces
  *   iter_outputs' model(None, X_test, None, single_eval_pos=None) (inference.py:499-507).
@@ -212,7 +226,8 @@ void mmpfn_cache_free(mmpfn_ctx* ctx, mmpfn_cache* cache);
 /* Measurement hook (no reference counterpart): while enabled, every sample-axis attention
  * launch of the bf16 forward is bracketed by HIP events on its own stream.  enable=1 clears
  * and starts a window, enable=0 stops it; _read synchronises and returns the summed launch
- * durations, the launch count and their algorithmic flops (4*T*(N+Q)*N*E each). */
+ * durations, the launch count and their algorithmic flops (4*T*(N+Q)*N*E each).  Only the full-shape
+ * launches count: a pruned last layer's one-column launch is neither bracketed nor added. */
 int mmpfn_kernel_timing(mmpfn_ctx* ctx, int enable);
 int mmpfn_kernel_timing_read(mmpfn_ctx* ctx, double* total_ms, int64_t* launches, double* flops);
 

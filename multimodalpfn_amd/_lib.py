@@ -127,6 +127,7 @@ SIGNATURES = [
                                       ctypes.POINTER(ctypes.c_double)]),
     ("mmpfn_siphash24_rows", _i, [_vp, _i64, _i64, _vp]),
     ("mmpfn_set_parity_attention_min_keys", _i, [_i, _i]),
+    ("mmpfn_set_full_last_layer", _i, [_vp, _i]),
 ]
 
 # include/mmpfn_modality.h (modality encoders: DINOv2 ViT, ELECTRA text tower)

@@ -526,6 +526,7 @@ __device__ __forceinline__ int a2_voff(int d, int c) { return d * 128 + 16 * (c 
 constexpr int A3_NCH = 2;
 constexpr int A3_QPW = 32 * A3_NCH;
 constexpr int A3_QPB = 4 * A3_QPW;
+static_assert(A3_QPB == ATTN_ITEM_QPB, "one task size for both kernels (capi.cpp item_sublayer aligns the pruned launch to it)");
 constexpr int A3_STAGE = 4 * 4096;  // K hi | K lo | V^T hi | V^T lo
 
 __device__ __forceinline__ void a3_split8(f32x4 a, f32x4 b, float sc, bf16x8& hi, bf16x8& lo) {

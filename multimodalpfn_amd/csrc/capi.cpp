@@ -55,7 +55,8 @@ struct Lane {
 // input encoders and the positional embeddings, so a predict runs only the test rows
 struct mmpfn_cache {
   int N = 0, F = 0, G = 0, C = 0, T = 0, Npad = 0, prec = 0, U = 0;
-  DevBuf kv;     // [L][K: T x Npad x 32 | V^T: T x 32 x Npad], element size of prec
+  DevBuf kv;     // [L][K: T x Npad x 32 | V^T: T x 32 x Npad], element size of prec; a pruned last layer writes
+                 // and reads column T-1 of layer L-1 only (its other columns: never written, never read)
   DevBuf slots;  // x-encoder SlotParams [G * fpg]
   DevBuf ymean;  // y-encoder train nanmean
   DevBuf uniq;   // sorted unique train labels [U]
@@ -95,6 +96,7 @@ struct mmpfn_ctx : Lane {  // the Lane base is the selected lane
   // recorded on the launching stream around every item-attention launch while enabled
   mmpfn_cache* cache_out = nullptr;       // being built by the current forward (train rows only)
   const mmpfn_cache* cache_in = nullptr;  // used by the current forward (test rows only)
+  bool full_last = false;  // mmpfn_set_full_last_layer: the forwards run their last layer in full
   bool kt_on = false;
   std::vector<hipEvent_t> kt_pool;  // event pairs, reused across windows
   size_t kt_used = 0;
@@ -509,7 +511,9 @@ int embed_cached(mmpfn_ctx* ctx, const mmpfn_cache* cc, const float* x, int S, i
 }
 
 // ---- attention between features (layer.py:332-339): X [M][T][S][E] <- LN(X + FeatAttn(X)), batch = row s
-int feat_sublayer(mmpfn_ctx* ctx, const LayerW& L, void* Xv, int S, int T, int M, PrecMode pm) {
+//      last: only the target token T-1 of every row is needed (a pruned last layer); the row-resident kernel then
+//      computes and stores that token alone, the other paths run in full
+int feat_sublayer(mmpfn_ctx* ctx, const LayerW& L, void* Xv, int S, int T, int M, PrecMode pm, bool last = false) {
   const mmpfn_model_desc& d = ctx->d;
   const int E = d.emsize, H = d.nhead;
   const int64_t R = (int64_t)S * T;
@@ -521,7 +525,8 @@ int feat_sublayer(mmpfn_ctx* ctx, const LayerW& L, void* Xv, int S, int T, int M
   if (b16 && T <= 64) {
     // one wave per row (all M members' rows in one launch), the whole sublayer in registers (featrow.hip); an
     // fp16 state always comes here (decode_prec keeps PREC_F16 to T <= 64)
-    HIPCHK(launch_feat_rows(Xv, pm.f16() ? L.feat_pack_f.p : L.feat_pack_h.p, S, T, M, E, H, d.ln_eps, st, pm.state()));
+    HIPCHK(launch_feat_rows(Xv, pm.f16() ? L.feat_pack_f.p : L.feat_pack_h.p, S, T, M, E, H, d.ln_eps, st, pm.state(),
+                            last));
     return MMPFN_OK;
   }
   float* Xall = (float*)Xv;
@@ -562,16 +567,43 @@ int feat_sublayer(mmpfn_ctx* ctx, const LayerW& L, void* Xv, int S, int T, int M
   return MMPFN_OK;
 }
 
+// ---- the item attention's out-projection: X <- LN(X + O Wout^T) over RM tokens (O: the attention output)
+int item_out_proj(mmpfn_ctx* ctx, const LayerW& L, const void* O, void* Xv, int64_t RM, PrecMode pm) {
+  const mmpfn_model_desc& d = ctx->d;
+  const int E = d.emsize;
+  hipStream_t st = ctx->stream;
+  if (pm.is16()) {
+    HIPCHK(launch_rowgemm_resln(O, pm.f16() ? L.item_out_f.p : L.item_out_h.p, RM, Xv, d.ln_eps, st, pm.state()));
+  } else if (pm.base == PREC_F32) {
+    HIPCHK(p3_resln(ctx, L.item_out, O, RM, (float*)Xv, st));
+  } else {
+    GemmArgs b = gargs();
+    b.A = O, b.lda = E, setw(ctx, b, L.item_out, L.item_out_h, pm.base);
+    b.M = (int)RM, b.N = E, b.K = E, b.X = (float*)Xv, b.ln_eps = d.ln_eps;
+    HIPCHK(launch_gemm(b, pm.base, EPI_RES_LN, true, true, 1, st));
+  }
+  return MMPFN_OK;
+}
+
 // ---- attention between items (layer.py:341-379) of layer l; rows of all members: logical row
 //      (member*T + t)*N + n -> memory row (member*T + t)*S + n, attention batch member*T + t.
 //      fuse_out: the out-projection + residual + LN is left to the MLP kernel's prologue (the
 //      attention output stays in ws_O); otherwise X <- LN(X + O Wout^T) here.
-int item_sublayer(mmpfn_ctx* ctx, int l, void* Xv, int S, int T, int N, int Npad, int M, PrecMode pm, bool fuse_out) {
+//      last: the pruned form of a forward's last layer (last_layer_tail): the target-token column T-1 of every
+//      member only -- M columns, T*S rows apart, into compact Q / K / V^T scratch and a compact O [M][S][E] -- and
+//      of its queries only the test rows; the out-projection is left to the caller.  The test rows keep the places
+//      they have in the full launch's 256-query tasks (the train rows that share their first task ride along), so
+//      every block that holds one sees the same queries and takes the same wave-wide re-run decisions as there.
+int item_sublayer(mmpfn_ctx* ctx, int l, void* Xv, int S, int T, int N, int Npad, int M, PrecMode pm, bool fuse_out,
+                  bool last = false) {
   const mmpfn_model_desc& d = ctx->d;
   const LayerW& L = ctx->layers[l];
   const int E = d.emsize, H = d.nhead, Q = S - N;
-  const int64_t RM = (int64_t)S * T * M;  // tokens of the batch
-  const int TM = T * M;                   // token columns of the batch (attention batches)
+  const int TM = last ? M : T * M;               // token columns of the batch (attention batches)
+  const int64_t RM = (int64_t)S * TM;            // tokens of the batch
+  const int64_t cs = last ? (int64_t)T * S : S;  // state rows between consecutive columns
+  const int c0 = last ? T - 1 : 0, nc = last ? 1 : T;  // the columns of one member, as the cache numbers them
+  if (last) Xv = (char*)Xv + (size_t)(T - 1) * S * E * pm.state_bytes();
   float* Xall = (float*)Xv;
   // the 16-bit modes run the row-resident projections and the pipelined attention; PREC_F16 in their F16 forms
   // (fp16 X and O, fp16 weight copies)
@@ -586,17 +618,18 @@ int item_sublayer(mmpfn_ctx* ctx, int l, void* Xv, int S, int T, int N, int Npad
   if (ctx->cache_in) {  // every row is a test row: Q only, against the cached train K/V of head 0
     const mmpfn_cache* cc = ctx->cache_in;
     const size_t kvl = (size_t)T * cc->Npad * 32 * eb;
-    const unsigned char* Kc = (const unsigned char*)cc->kv.p + (size_t)l * 2 * kvl;
+    const size_t ccol = (size_t)c0 * cc->Npad * 32 * eb;  // the first column's K (V^T) block inside the layer's
+    const unsigned char* Kc = (const unsigned char*)cc->kv.p + (size_t)l * 2 * kvl + ccol;
     const unsigned char* Vc = Kc + kvl;
     if (b16) {
-      HIPCHK(launch_rowgemm_qkv(Xv, S, S, 1, 0, h16 ? L.item_qtest_f.p : L.item_qtest_h.p, TM * S, E, Qi, Ki, Vi, S,
+      HIPCHK(launch_rowgemm_qkv(Xv, S, cs, 1, 0, h16 ? L.item_qtest_f.p : L.item_qtest_h.p, TM * S, E, Qi, Ki, Vi, S,
                                 Npad, H, st, pm.state(), pm.qk()));
     } else if (pm.base == PREC_F32) {
-      const Proj3Set ps = p3set(ctx, L.item_qtest, Xall, S, S, 1, 0, (int64_t)TM * S, E);
+      const Proj3Set ps = p3set(ctx, L.item_qtest, Xall, S, cs, 1, 0, (int64_t)TM * S, E);
       HIPCHK(launch_proj3_qkv(&ps, 1, Qi, Ki, Vi, S, Npad, H, st));
     } else {
       GemmArgs c = gargs();
-      c.A = Xall, c.lda = E, c.a_rdiv = S, c.a_rmul = S, c.a_roff = 0;
+      c.A = Xall, c.lda = E, c.a_rdiv = S, c.a_rmul = cs, c.a_roff = 0;
       setw(ctx, c, L.item_qtest, L.item_qtest_h, pm.base);
       c.M = TM * S, c.N = E, c.K = E;
       c.q = Qi, c.k = Ki, c.v = Vi, c.S = S, c.Npad = Npad, c.T = TM, c.H = H;
@@ -615,15 +648,15 @@ int item_sublayer(mmpfn_ctx* ctx, int l, void* Xv, int S, int T, int N, int Npad
     if (b16) {  // row-resident projections straight into the attention layouts
       // train rows q|k|v and test rows q in one launch (test-row blocks last)
       HIPCHK(launch_rowgemm_qkv_pair(Xv, N, 0, h16 ? L.item_qkv_f.p : L.item_qkv_h.p, TM * N, 3 * E, Q, N,
-                                     h16 ? L.item_qtest_f.p : L.item_qtest_h.p, TM * Q, E, S, Qi, Ki, Vi, S, Npad, H, st,
+                                     h16 ? L.item_qtest_f.p : L.item_qtest_h.p, TM * Q, E, cs, Qi, Ki, Vi, S, Npad, H, st,
                                      pm.state(), pm.qk()));
     } else if (pm.base == PREC_F32) {  // train rows q|k|v and test rows q in one launch
-      const Proj3Set ps[2] = {p3set(ctx, L.item_qkv, Xall, N, S, 1, 0, (int64_t)TM * N, 3 * E),
-                              p3set(ctx, L.item_qtest, Xall, Q > 0 ? Q : 1, S, 1, N, (int64_t)TM * Q, E)};
+      const Proj3Set ps[2] = {p3set(ctx, L.item_qkv, Xall, N, cs, 1, 0, (int64_t)TM * N, 3 * E),
+                              p3set(ctx, L.item_qtest, Xall, Q > 0 ? Q : 1, cs, 1, N, (int64_t)TM * Q, E)};
       HIPCHK(launch_proj3_qkv(ps, 2, Qi, Ki, Vi, S, Npad, H, st));
     } else {
       GemmArgs a = gargs();
-      a.A = Xall, a.lda = E, a.a_rdiv = N, a.a_rmul = S, a.a_roff = 0;
+      a.A = Xall, a.lda = E, a.a_rdiv = N, a.a_rmul = cs, a.a_roff = 0;
       setw(ctx, a, L.item_qkv, L.item_qkv_h, pm.base);
       a.M = TM * N, a.N = 3 * E, a.K = E;
       a.q = Qi, a.k = Ki, a.v = Vi, a.S = S, a.Npad = Npad, a.T = TM, a.H = H;
@@ -639,16 +672,18 @@ int item_sublayer(mmpfn_ctx* ctx, int l, void* Xv, int S, int T, int N, int Npad
     if (ctx->cache_out) {  // keep head 0's K / V^T of every column (the test rows' KV, layer.py:344-358)
       mmpfn_cache* cc = ctx->cache_out;
       const size_t blk = (size_t)Npad * 32 * eb, kvl = (size_t)T * blk;
-      unsigned char* Kc = (unsigned char*)cc->kv.p + (size_t)l * 2 * kvl;
-      HIPCHK(hipMemcpy2DAsync(Kc, blk, Ki, (size_t)H * blk, blk, T, hipMemcpyDeviceToDevice, st));
-      HIPCHK(hipMemcpy2DAsync(Kc + kvl, blk, Vi, (size_t)H * blk, blk, T, hipMemcpyDeviceToDevice, st));
+      unsigned char* Kc = (unsigned char*)cc->kv.p + (size_t)l * 2 * kvl + c0 * blk;
+      HIPCHK(hipMemcpy2DAsync(Kc, blk, Ki, (size_t)H * blk, blk, nc, hipMemcpyDeviceToDevice, st));
+      HIPCHK(hipMemcpy2DAsync(Kc + kvl, blk, Vi, (size_t)H * blk, blk, nc, hipMemcpyDeviceToDevice, st));
     }
+    if (last && Q == 0) return MMPFN_OK;  // (a cache build: nothing reads the last layer's train-row outputs)
     // train rows (own heads) and test rows (head-0 K/V, MQA)
     AttnLayerArgs a{Qi, Ki, Vi, O, S, TM, H, Npad, N};
     a.a0 = 0, a.na = N, a.b0 = N, a.nb = Q, a.kvb = 0;
+    if (last) a.na = N % ATTN_ITEM_QPB, a.a0 = N - a.na;
     if (b16) {  // in one launch
       hipEvent_t* ev = nullptr;
-      if (ctx->kt_on) {
+      if (ctx->kt_on && !last) {  // (the roofline's launches all have the full layer's shape)
         if (ctx->kt_used + 2 > ctx->kt_pool.size()) {
           for (int i = 0; i < 64; ++i) {
             hipEvent_t e;
@@ -672,22 +707,12 @@ int item_sublayer(mmpfn_ctx* ctx, int l, void* Xv, int S, int T, int N, int Npad
     } else if (pm.base == PREC_F32) {  // parity mode: split-bf16 products, train and test rows in one launch
       HIPCHK(launch_attn_item3(a, st));
     } else {
-      HIPCHK(launch_attn_item(Qi, Ki, Vi, O, S, TM, H, Npad, 0, N, N, -1, pm.base, st));
+      if (!last) HIPCHK(launch_attn_item(Qi, Ki, Vi, O, S, TM, H, Npad, 0, N, N, -1, pm.base, st));
       if (Q > 0) HIPCHK(launch_attn_item(Qi, Ki, Vi, O, S, TM, H, Npad, N, Q, N, 0, pm.base, st));
     }
   }
-  if (fuse_out) return MMPFN_OK;
-  if (b16) {
-    HIPCHK(launch_rowgemm_resln(O, h16 ? L.item_out_f.p : L.item_out_h.p, RM, Xv, d.ln_eps, st, pm.state()));
-  } else if (pm.base == PREC_F32) {
-    HIPCHK(p3_resln(ctx, L.item_out, O, RM, Xall, st));
-  } else {
-    GemmArgs b = gargs();
-    b.A = O, b.lda = E, setw(ctx, b, L.item_out, L.item_out_h, pm.base);
-    b.M = (int)RM, b.N = E, b.K = E, b.X = Xall, b.ln_eps = d.ln_eps;
-    HIPCHK(launch_gemm(b, pm.base, EPI_RES_LN, true, true, 1, st));
-  }
-  return MMPFN_OK;
+  if (fuse_out || last) return MMPFN_OK;
+  return item_out_proj(ctx, L, O, Xv, RM, pm);
 }
 
 // ---- MLP (mlp.py:93-104) + residual + LN over RM tokens; O non-null (the 16-bit modes): the item attention's
@@ -720,6 +745,41 @@ int run_layer(mmpfn_ctx* ctx, int l) {
   RC(feat_sublayer(ctx, L, Xall, S, T, M, pm));
   RC(item_sublayer(ctx, l, Xall, S, T, N, Npad, M, pm, fuse));
   return mlp_sublayer(ctx, L, Xall, (int64_t)S * T * M, pm, fuse ? ctx->ws_O.p : nullptr);
+}
+
+// The last layer of a forward, pruned to what the decoder reads: the test rows [N, S) of the target token (column
+// T-1) of every member.  Exact, since every kernel computes a state row from that row's own inputs:
+//   feature attention   every row (a test row's target token attends over the row's tokens; a train row's is the
+//                       K / V of column T-1), its output at token T-1 (the row-resident kernel's LAST form computes
+//                       only that one; the T > 64 and fp32 paths run in full);
+//   item attention      column T-1 only: K / V^T of its train rows, Q of its test rows (item_sublayer, last);
+//   out-projection, MLP the Q test rows of that column, member by member.
+// Afterwards the state holds this layer's output at those rows only; every other row is left as this layer's
+// feature attention or the layer before wrote it.
+int last_layer_tail(mmpfn_ctx* ctx, int l) {
+  const LayerW& L = ctx->layers[l];
+  const int S = ctx->S, T = ctx->T, N = ctx->N, Npad = ctx->Npad, M = ctx->M, E = ctx->d.emsize;
+  const PrecMode pm = lane_prec(*ctx);
+  const bool fuse = pm.is16();
+  RC(feat_sublayer(ctx, L, ctx->ws_X.p, S, T, M, pm, true));
+  RC(item_sublayer(ctx, l, ctx->ws_X.p, S, T, N, Npad, M, pm, fuse, true));
+  const int64_t Q = S - N;
+  if (Q == 0) return MMPFN_OK;
+  const size_t ob = fuse ? 2 : 4;  // the attention output's element: 16-bit in the 16-bit modes
+  for (int m = 0; m < M; ++m) {
+    void* X = (char*)ctx->ws_X.p + (((size_t)m * T + T - 1) * S + N) * E * pm.state_bytes();
+    const void* O = (const char*)ctx->ws_O.p + ((size_t)m * S + N) * E * ob;  // compact: one column per member
+    if (!fuse) RC(item_out_proj(ctx, L, O, X, Q, pm));
+    RC(mlp_sublayer(ctx, L, X, Q, pm, fuse ? O : nullptr));
+  }
+  return MMPFN_OK;
+}
+
+// every layer of a forward entry point: the last one pruned unless mmpfn_set_full_last_layer asked for it in full
+int run_forward_layers(mmpfn_ctx* ctx) {
+  const int nl = ctx->d.nlayers;
+  for (int l = 0; l < nl; ++l) RC(l == nl - 1 && !ctx->full_last ? last_layer_tail(ctx, l) : run_layer(ctx, l));
+  return MMPFN_OK;
 }
 
 // workspace of the selected lane for a per-sublayer tap on a caller-provided state of S x T tokens
@@ -1068,7 +1128,7 @@ int mmpfn_forward(mmpfn_ctx* ctx, const float* x, int S, int F, const float* tok
   if (!ctx || !logits) return MMPFN_ERR_INVALID;
   HIPCHK(hipSetDevice(ctx->device));
   RC(embed(ctx, x, S, F, tokens, C, y, N, uniq, U, pos_rand, precision));
-  for (int l = 0; l < ctx->d.nlayers; ++l) RC(run_layer(ctx, l));
+  RC(run_forward_layers(ctx));
   return decode(ctx, logits);
 }
 
@@ -1080,7 +1140,7 @@ int mmpfn_forward_batch(mmpfn_ctx* ctx, int M, const float* const* x, int S, int
   HIPCHK(hipSetDevice(ctx->device));
   for (int m = 0; m < M; ++m)
     RC(embed(ctx, F > 0 ? x[m] : nullptr, S, F, tokens, C, y[m], N, uniq[m], U[m], pos_rand, precision, m, M));
-  for (int l = 0; l < ctx->d.nlayers; ++l) RC(run_layer(ctx, l));
+  RC(run_forward_layers(ctx));
   return decode(ctx, logits, M);
 }
 
@@ -1175,15 +1235,9 @@ int mmpfn_cache_build(mmpfn_ctx* ctx, const float* x, int N, int F, const float*
     HIPCHK(hipMemcpyAsync(cc->uniq.p, uniq, (size_t)U * 4, hipMemcpyDeviceToDevice, st));
     HIPCHK(hipMemcpyAsync(cc->pe.p, ctx->ws_pe.p, (size_t)(cc->G + C) * E * 4, hipMemcpyDeviceToDevice, st));
     ctx->cache_out = cc;
-    for (int l = 0; l < d.nlayers; ++l) {
-      const int rc = run_layer(ctx, l);
-      if (rc) {
-        ctx->cache_out = nullptr;
-        return rc;
-      }
-    }
+    const int rc = run_forward_layers(ctx);
     ctx->cache_out = nullptr;
-    return MMPFN_OK;
+    return rc;
   };
   const int rc = build();
   if (rc) {
@@ -1201,14 +1255,9 @@ int mmpfn_cache_predict(mmpfn_ctx* ctx, const mmpfn_cache* cache, const float* x
   HIPCHK(hipSetDevice(ctx->device));
   RC(embed_cached(ctx, cache, x, Q, F, tokens, C));
   ctx->cache_in = cache;
-  for (int l = 0; l < ctx->d.nlayers; ++l) {
-    const int rc = run_layer(ctx, l);
-    if (rc) {
-      ctx->cache_in = nullptr;
-      return rc;
-    }
-  }
+  const int rc = run_forward_layers(ctx);
   ctx->cache_in = nullptr;
+  if (rc) return rc;
   return decode(ctx, logits);
 }
 
@@ -1227,6 +1276,12 @@ void mmpfn_cache_free(mmpfn_ctx* ctx, mmpfn_cache* cache) {
 }
 
 int mmpfn_set_parity_attention_min_keys(int n, int form) { return mmpfn::set_x3_cheap_min_keys(n, form); }
+
+int mmpfn_set_full_last_layer(mmpfn_ctx* ctx, int on) {
+  if (!ctx) return MMPFN_ERR_INVALID;
+  ctx->full_last = on != 0;
+  return MMPFN_OK;
+}
 
 int mmpfn_kernel_timing(mmpfn_ctx* ctx, int enable) {
   if (!ctx) return MMPFN_ERR_INVALID;

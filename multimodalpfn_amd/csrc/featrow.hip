@@ -68,10 +68,15 @@ __device__ __forceinline__ void fr_dma16(uint32_t voff, const void* sbase, unsig
 }
 #pragma clang diagnostic pop
 
-template <int NT, bool F16>
+// LAST: the form of a forward's pruned last layer (capi.cpp last_layer_tail), which reads this sublayer's output at
+// the target token T-1 only: K and V of every token tile as ever, but Q, the softmax, P.V and the out-projection
+// for the one query tile that holds token T-1 (the last tile: T > 16 (NT - 1)), and the store for that token alone.
+// A tile's MFMA chains do not depend on the other tiles', so token T-1 comes out bit for bit as in the full form.
+template <int NT, bool F16, bool LAST = false>
 __global__ __launch_bounds__(256, NT <= 3 ? 2 : 1) void feat_rows_kernel(void* __restrict__ Xv,
                                                                          const void* __restrict__ packv, int S, int T,
                                                                          int M, float eps) {
+  constexpr int Q0 = LAST ? NT - 1 : 0;  // first query tile
   typedef typename Op16<F16>::x8 X8;
   typedef std::conditional_t<F16, f16, float> XT;  // state element
   typedef typename Op16<F16>::t WT;
@@ -147,7 +152,7 @@ __global__ __launch_bounds__(256, NT <= 3 ? 2 : 1) void feat_rows_kernel(void* _
   dma_wait();
   __syncthreads();
 
-  X8 of[FR_H][NT];  // O^T fragments of every head (K-step h of the out-projection)
+  X8 of[FR_H][NT - Q0];  // O^T fragments of every head (K-step h of the out-projection), query tiles Q0 ..
 #pragma unroll
   for (int h = 0; h < FR_H; ++h) {
     // the next image: head h+1's QKV, or after the last head the out-projection image's first half (buffer 0
@@ -176,9 +181,11 @@ __global__ __launch_bounds__(256, NT <= 3 ? 2 : 1) void feat_rows_kernel(void* _
 #pragma unroll
         for (int f = 0; f < 2; ++f) wqf[f] = *(const X8*)(wq + (32 * j + 16 * f + n) * FR_ST + 32 * ks + 8 * g);
 #pragma unroll
-        for (int tt = 0; tt < NT; ++tt)
+        for (int tt = 0; tt < NT; ++tt) {
+          if (j == 0 && tt < Q0) continue;  // (Q of the query tiles only)
 #pragma unroll
           for (int f = 0; f < 2; ++f) qa[f][tt] = mfma16x(wqf[f], xf[tt][ks], qa[f][tt]);
+        }
         if constexpr (SPREAD) {  // pieces 0 .. 9 after the Q and K k-steps 0 .. 4 of each
           if (ks < FR_PPW / 2) dma_piece(nsrc, ndst, j * (FR_PPW / 2) + ks);
         }
@@ -217,7 +224,7 @@ __global__ __launch_bounds__(256, NT <= 3 ? 2 : 1) void feat_rows_kernel(void* _
 
     // ---- per query tile: S^T[key][query] = K Q^T (log2 units), softmax over keys, O^T = V^T P^T
 #pragma unroll
-    for (int qt = 0; qt < NT; ++qt) {
+    for (int qt = Q0; qt < NT; ++qt) {
       f32x4 st[NT];
 #pragma unroll
       for (int kt = 0; kt < NT; ++kt) st[kt] = mfma16x(kf[kt], qf[qt], f32x4{0.f, 0.f, 0.f, 0.f});
@@ -247,7 +254,7 @@ __global__ __launch_bounds__(256, NT <= 3 ? 2 : 1) void feat_rows_kernel(void* _
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) oa[mt] = mfma16x(vfr[mt][kp], pb, oa[mt]);
       }
-      of[h][qt] = cat8<X8>(oa[0], oa[1], inv);
+      of[h][qt - Q0] = cat8<X8>(oa[0], oa[1], inv);
       __builtin_amdgcn_sched_barrier(0);
     }
     dma_wait();  // the next image landed (every wave's pieces: the barrier below); this head's buffer is free
@@ -263,18 +270,18 @@ __global__ __launch_bounds__(256, NT <= 3 ? 2 : 1) void feat_rows_kernel(void* _
   // ---- per token tile: Y^T = Wout . O^T over K = 192 (K-step h = head h), image [192][FR_ST],
   //      then residual + LayerNorm per token (lane = token n, 48 of its 192 features)
 #pragma unroll
-  for (int tt = 0; tt < NT; ++tt) {
+  for (int tt = Q0; tt < NT; ++tt) {
     f32x4 y[FR_E / 16];
 #pragma unroll
     for (int f = 0; f < FR_E / 16; ++f) {
       y[f] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int h = 0; h < FR_H; ++h)
-        y[f] = mfma16x(*(const X8*)(wbuf + (16 * f + n) * FR_ST + 32 * h + 8 * g), of[h][tt], y[f]);
+        y[f] = mfma16x(*(const X8*)(wbuf + (16 * f + n) * FR_ST + 32 * h + 8 * g), of[h][tt - Q0], y[f]);
     }
     const int t = 16 * tt + n;
     const bool pad = tt == NT - 1 && t >= T;
-    const bool valid = rowok && !pad;
+    const bool valid = rowok && !pad && (!LAST || t == T - 1);
     // fp32 state: the residual / output pieces are 4 features at 16 f + 4 g (the Y^T rows of the lane)
     char* const xr = (char*)xrow + xoff[tt] - 16 * g;
     float sm = 0.f;
@@ -330,22 +337,26 @@ __global__ __launch_bounds__(256, NT <= 3 ? 2 : 1) void feat_rows_kernel(void* _
   }
 }
 
-template <bool F16>
+template <bool F16, bool LAST>
 hipError_t launch_fr(void* X, const void* pk, int S, int T, int M, float eps, hipStream_t st) {
   const dim3 grid((M * S + 3) / 4), block(256);
-  if (T <= 16) hipLaunchKernelGGL((feat_rows_kernel<1, F16>), grid, block, 0, st, X, pk, S, T, M, eps);
-  else if (T <= 32) hipLaunchKernelGGL((feat_rows_kernel<2, F16>), grid, block, 0, st, X, pk, S, T, M, eps);
-  else if (T <= 48) hipLaunchKernelGGL((feat_rows_kernel<3, F16>), grid, block, 0, st, X, pk, S, T, M, eps);
-  else hipLaunchKernelGGL((feat_rows_kernel<4, F16>), grid, block, 0, st, X, pk, S, T, M, eps);
+  if (T <= 16) hipLaunchKernelGGL((feat_rows_kernel<1, F16, LAST>), grid, block, 0, st, X, pk, S, T, M, eps);
+  else if (T <= 32) hipLaunchKernelGGL((feat_rows_kernel<2, F16, LAST>), grid, block, 0, st, X, pk, S, T, M, eps);
+  else if (T <= 48) hipLaunchKernelGGL((feat_rows_kernel<3, F16, LAST>), grid, block, 0, st, X, pk, S, T, M, eps);
+  else hipLaunchKernelGGL((feat_rows_kernel<4, F16, LAST>), grid, block, 0, st, X, pk, S, T, M, eps);
   return hipGetLastError();
 }
 }  // namespace
 
 hipError_t launch_feat_rows(void* X, const void* pack, int S, int T, int M, int E, int H, float eps, hipStream_t st,
-                            DType x_t) {
+                            DType x_t, bool last) {
   if (S <= 0 || M <= 0) return hipSuccess;
   if (E != FR_E || H != FR_H || T < 1 || T > 64 || x_t == DType::BF16) return hipErrorInvalidValue;
-  return x_t == DType::F16 ? launch_fr<true>(X, pack, S, T, M, eps, st) : launch_fr<false>(X, pack, S, T, M, eps, st);
+  if (last)
+    return x_t == DType::F16 ? launch_fr<true, true>(X, pack, S, T, M, eps, st)
+                             : launch_fr<false, true>(X, pack, S, T, M, eps, st);
+  return x_t == DType::F16 ? launch_fr<true, false>(X, pack, S, T, M, eps, st)
+                           : launch_fr<false, false>(X, pack, S, T, M, eps, st);
 }
 
 }  // namespace mmpfn

@@ -159,8 +159,9 @@ hipError_t launch_proj3_resln(const float* O, const void* W, int64_t w_lo, int64
 // X holds M members [M][T][S][E]; one launch covers the M*S rows
 // x_t: the state's type, fp32 (bf16 images) or fp16 (PREC_F16: the fp16 images with the out-projection rows permuted,
 // pack_feat_rows res_perm)
+// last: only token T-1 of every row is computed and stored (the pruned last layer; bit for bit the full form's)
 hipError_t launch_feat_rows(void* X, const void* pack, int S, int T, int M, int E, int H, float eps, hipStream_t st,
-                            DType x_t = DType::F32);
+                            DType x_t = DType::F32, bool last = false);
 
 // ---- attention -------------------------------------------------------------------
 // generic MFMA attention over a batch (blockIdx.z) of independent sequences:

@@ -94,6 +94,9 @@ def _lane_stream(device: torch.device, k: int) -> torch.cuda.Stream:
 
 DEFAULT_LANES = int(os.environ.get("MMPFN_LANES", "2"))  # concurrent member lanes of forward_many
 DEFAULT_BATCH = int(os.environ.get("MMPFN_BATCH", "1"))  # members per batched forward of forward_many (1: DESIGN 7)
+# 1: the forwards run their last layer in full instead of pruned to the rows the decoder reads (the
+# same logits bit for bit -- the pruned form's reference and A/B handle)
+DEFAULT_FULL_LAST_LAYER = os.environ.get("MMPFN_FULL_LAST_LAYER") == "1"
 _DEBUG_SYNC = os.environ.get("MMPFN_DEBUG_SYNC") == "1"  # diagnostics: serialise forward_many's units
 _DEBUG_KEEP = os.environ.get("MMPFN_DEBUG_KEEP") == "1"  # diagnostics: keep every prepared input alive
 _KEEP: list = []
@@ -136,6 +139,7 @@ class HipEngine:
         self._streams: list = []
         self.lanes = DEFAULT_LANES
         self.batch = DEFAULT_BATCH
+        self.full_last_layer = DEFAULT_FULL_LAST_LAYER
         self.refs = 1  # model copies holding this engine (PerFeatureTransformer.__deepcopy__ shares it)
         self.serial = next(_SERIAL)
 
@@ -148,6 +152,17 @@ class HipEngine:
 
     def _bind_stream(self) -> None:
         self._check(self.lib.mmpfn_set_stream(self.ctx, ctypes.c_void_p(self._stream())), "mmpfn_set_stream")
+
+    @property
+    def full_last_layer(self) -> bool:
+        """Whether ``forward`` / ``forward_batch`` / ``cache_build`` / ``cache_predict`` run the last layer in full
+        (``mmpfn_set_full_last_layer``).  Off by default: they compute only the target token's test rows there."""
+        return self._full_last_layer
+
+    @full_last_layer.setter
+    def full_last_layer(self, on: bool) -> None:
+        self._check(self.lib.mmpfn_set_full_last_layer(self.ctx, int(bool(on))), "mmpfn_set_full_last_layer")
+        self._full_last_layer = bool(on)
 
     def release(self) -> None:
         """Drop one holder's reference; the context is destroyed with the last one."""
