@@ -70,8 +70,17 @@ def pos_rand(cfg: ModelConfig, n_tokens: int, device: torch.device | None = None
 def target_uniques(y_train: np.ndarray) -> np.ndarray:
     """Sorted unique train targets after the y NaN fill (encoders.py:461-493,954-958)."""
     y = np.asarray(y_train, dtype=np.float32)
-    if np.isnan(y).any():
-        y = np.where(np.isnan(y), np.float32(np.nanmean(y)), y)
+    nan = np.isnan(y)
+    if nan.any():
+        # the fill must be the value the device fills with (enc_stats_kernel's label block): the float64 sum
+        # over the count, rounded to float32 once.  A float32 np.nanmean can land one ulp below it; the filled
+        # rows then compare greater than their own entry here and every NaN-label row (every test row) codes
+        # one class too high.  (A float64 sum of float32 labels is exact, so the same in any order, as long as
+        # their count times their dynamic range stays below 2^29.)
+        ok = y[~nan].astype(np.float64)
+        with np.errstate(invalid="ignore"):
+            fill = np.float32(ok.sum() / np.float64(ok.size))
+        y = np.where(nan, fill, y)
     return np.unique(y).astype(np.float32)
 
 

@@ -84,7 +84,7 @@ def _nanstd(x: torch.Tensor) -> torch.Tensor:
 # --------------------------------------------------------------------------------------
 
 
-def encode_x(spec: OracleSpec, w: dict, x: torch.Tensor, n_train: int) -> torch.Tensor:
+def encode_x(spec: OracleSpec, w: dict, x: torch.Tensor, n_train: int, taps: dict | None = None) -> torch.Tensor:
     """x encoder: ``[S, F]`` -> ``[S, G, E]``.
 
     Steps (``get_encoder`` T/loading.py:308-371):
@@ -99,6 +99,9 @@ def encode_x(spec: OracleSpec, w: dict, x: torch.Tensor, n_train: int) -> torch.
     ``nf`` is the encoder width (checkpoint ``config.features_per_group``,
     T/loading.py:473-475); ``fpg`` is the model's grouping (yaml
     ``features_per_group``), which may be smaller (salary: 1).
+
+    ``taps`` (optional) receives the discrete decisions: ``x_selected`` (step 0's non-constant mask ``[G, fpg]``)
+    and ``x_used`` (step 4's ``[G, fpg]``).
     """
     S, Fdim = x.shape
     fpg = spec.features_per_group
@@ -148,6 +151,8 @@ def encode_x(spec: OracleSpec, w: dict, x: torch.Tensor, n_train: int) -> torch.
     # 4: rescale by the number of used (non-constant) features per group
     sel2 = (x[1:] == x[0:1]).sum(0) != (S - 1)  # [G, fpg]
     used = torch.clip(sel2.sum(-1, keepdim=True), min=1).to(x.dtype)  # [G, 1]
+    if taps is not None:
+        taps["x_selected"], taps["x_used"] = sel.clone(), sel2.clone()
     nf = spec.encoder_features
     x = x * torch.sqrt(nf / used)
     if nf > fpg:  # VariableNumFeatures zero-padding of main and nan indicators
@@ -161,12 +166,12 @@ def encode_x(spec: OracleSpec, w: dict, x: torch.Tensor, n_train: int) -> torch.
     return feats @ W.to(x.dtype).T
 
 
-def encode_y(spec: OracleSpec, w: dict, y_train: torch.Tensor, S: int) -> torch.Tensor:
+def encode_y(spec: OracleSpec, w: dict, y_train: torch.Tensor, S: int, taps: dict | None = None) -> torch.Tensor:
     """y encoder: ``[N]`` -> ``[S, E]`` (T/loading.py:374-398).
 
     NaN-pad test rows (T/transformer.py:682-718), NanHandling (fill with train
     mean, indicator -2), class-index target encoding ``(y > unique_train).sum()``
-    (T/encoders.py:954-974), Linear(2 -> E, bias).
+    (T/encoders.py:954-974), Linear(2 -> E, bias).  ``taps`` (optional) receives the class codes ``y_codes`` ``[S]``.
     """
     N = y_train.shape[0]
     y = torch.full((S,), float("nan"), dtype=y_train.dtype, device=y_train.device)
@@ -176,6 +181,8 @@ def encode_y(spec: OracleSpec, w: dict, y_train: torch.Tensor, S: int) -> torch.
     y = torch.where(torch.isnan(y), mean, y)
     uniq = torch.unique(y[:N])
     yc = (y.unsqueeze(-1) > uniq).sum(-1).to(y.dtype)
+    if taps is not None:
+        taps["y_codes"] = yc.clone()
     feats = torch.stack([yc, ind], -1)
     W = w["y_encoder.2.layer.weight"].to(y.dtype)
     b = w["y_encoder.2.layer.bias"].to(y.dtype)
@@ -368,20 +375,20 @@ def layer_forward(spec: OracleSpec, w: dict, l: int, X: torch.Tensor, n_train: i
     return mlp_sublayer(spec, w, l, X)
 
 
-def embed_inputs(spec, w, x, image, y_train, dtype=torch.float32, mixer_tokens=None):
-    """Build the transformer input ``[S, T, E]`` (T/transformer.py:586-797)."""
+def embed_inputs(spec, w, x, image, y_train, dtype=torch.float32, mixer_tokens=None, taps=None):
+    """Build the transformer input ``[S, T, E]`` (T/transformer.py:586-797); ``taps``: see the encoders."""
     N = y_train.shape[0]
     S = x.shape[0] if x is not None else image.shape[0]
     parts = []
     if x is not None:
-        parts.append(encode_x(spec, w, x.to(dtype), N))
+        parts.append(encode_x(spec, w, x.to(dtype), N, taps))
     if image is not None:
         if mixer_tokens is None:
             mixer_tokens = oracle_mixer(spec, w, image.to(dtype))
         parts.append(mixer_tokens.to(dtype))
     tok = torch.cat(parts, dim=1)  # token_append (T/transformer.py:1038)
     tok = tok + subspace_pos_emb(spec, w, tok.shape[1], dtype).unsqueeze(0)
-    ytok = encode_y(spec, w, y_train.to(dtype), S)
+    ytok = encode_y(spec, w, y_train.to(dtype), S, taps)
     X = torch.cat([tok, ytok.unsqueeze(1)], dim=1)
     if torch.isnan(X).any():  # T/transformer.py:790-796
         raise ValueError("There should be no NaNs in the encoded x and y.")
