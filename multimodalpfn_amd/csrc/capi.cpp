@@ -28,14 +28,26 @@ using namespace mmpfn;
 
 namespace {
 
-struct LayerW {  // packed per layer, [N][K] row-major
-  DevBuf feat_qkv, feat_out, item_qkv, item_qtest, item_out, mlp1, mlp2;  // fp32
-  DevBuf feat_qkv_h, feat_out_h, item_qkv_h, item_qtest_h, item_out_h, mlp1_h, mlp2_h;  // bf16
-  DevBuf feat_pack_h;  // bf16 LDS images of the feature-attention weights (featrow.hip)
-  // PREC_F16 (fp16): feature-attention images (out-projection rows in f16_row_perm order), item q|k|v and
-  // test q (Q rows prescaled like the bf16 copies), item out-projection and MLP W2 with f16_row_perm rows,
-  // MLP W1 natural
-  DevBuf feat_pack_f, item_qkv_f, item_qtest_f, item_out_f, mlp1_f, mlp2_f;
+// The weights of one finalised model, every one [N][K] row-major in each form its kernels read (Weight); the orders
+// of the forms are stated where they are filled (the finalize_* functions).  Built afresh by every finalize, so
+// nothing of an earlier model survives one.
+struct LayerW {
+  Weight feat_qkv, feat_out, item_qkv, item_qtest, item_out, mlp1, mlp2;
+  Weight feat_pack;  // 16-bit LDS images of the feature-attention weights (featrow.hip)
+};
+
+struct HeadBank {  // the MGM heads or the MoE experts, stacked
+  Weight w1, w2;
+  DevBuf b1, b2;
+};
+struct ModelWeights {
+  std::vector<LayerW> layers;
+  DevBuf enc_w, y_w, y_b, pe_w, pe_b, dec_b1, dec_b2;
+  Weight dec_w1, dec_w2;  // 16-bit forms (the MFMA decoder) only where n_out <= 16 && nhid % 128 == 0
+  HeadBank mgm, moe;      // fp16 forms (PREC_F16's MGM head bank) only in mgm_f16_shape
+  DevBuf moe_gw, moe_gb;
+  Weight cap_kv, cap_o, cap_f0, cap_f3;
+  DevBuf cap_qp, cap_kv_b, cap_o_b, cap_f0_b, cap_f3_b, cap_ng, cap_nb, cap_vecs;  // vecs: [bo | b0 | g | b + b3]
 };
 
 // per-member forward state of one lane: independent forward workspaces sharing the weights, so members can run
@@ -74,17 +86,7 @@ struct mmpfn_ctx : Lane {  // the Lane base is the selected lane
   mmpfn_model_desc d{};
   std::map<std::string, std::vector<float>> host;
 
-  std::vector<LayerW> layers;
-  // parity mode (PREC_F32): every GEMM weight also as bf16 hi | lo planes, keyed by its fp32 copy
-  std::map<const void*, DevBuf> split;
-  DevBuf enc_w, y_w, y_b, pe_w, pe_b, dec_w1, dec_b1, dec_w2, dec_b2;
-  DevBuf dec_w1_h, dec_w1_f, dec_w2p_h, dec_w2p_f;  // 16-bit decoder: W1 [Fh][E], W2 [16][Fh] permuted
-  // mixer
-  DevBuf mgm_w1, mgm_w1_h, mgm_w1_f, mgm_b1, mgm_w2, mgm_w2_h, mgm_w2_f, mgm_b2;
-  DevBuf cap_qp, cap_kv, cap_kv_h, cap_kv_b, cap_o, cap_o_h, cap_o_b, cap_f0, cap_f0_h, cap_f0_b, cap_f3, cap_f3_h,
-      cap_f3_b, cap_ng, cap_nb;
-  DevBuf cap_f0_p, cap_f3_p, cap_vecs;  // the FFN in mlp_rows order (bf16) and [bo | b0 | g | b + b3]
-  DevBuf moe_w1, moe_w1_h, moe_b1, moe_w2, moe_w2_h, moe_b2, moe_gw, moe_gb;
+  ModelWeights w;
 
   DevBuf mx[8];
   DevBuf tap_v8;   // e4m3 V^T of the fp8 attention tap
@@ -121,60 +123,34 @@ int ensure_flag(mmpfn_ctx* ctx, DevBuf& b, hipStream_t st) {
   return MMPFN_OK;
 }
 
-// bf16 hi | lo planes of v (hi = bf16(w), lo = bf16(w - hi)), the weight operand of the parity mode's
-// three-product GEMMs, stored under the key of its fp32 copy f
-int upsplit(mmpfn_ctx* ctx, const DevBuf& f, const std::vector<float>& v) {
-  std::vector<uint16_t> h(2 * v.size());
-  for (size_t i = 0; i < v.size(); ++i) {
-    const uint16_t hi = f2bf(v[i]);
-    uint32_t u = (uint32_t)hi << 16;
-    float fh;
-    std::memcpy(&fh, &u, 4);
-    h[i] = hi;
-    h[v.size() + i] = f2bf(v[i] - fh);
-  }
-  DevBuf& b = ctx->split[f.p];
-  RC(ensure(ctx, b, h.size() * 2));
-  b.n = v.size();
-  HIPCHK(hipMemcpy(b.p, h.data(), h.size() * 2, hipMemcpyHostToDevice));
-  return MMPFN_OK;
-}
-
-int up2(mmpfn_ctx* ctx, DevBuf& f, DevBuf& h, const std::vector<float>& v) {
-  RC(upload(ctx, f, v));
-  RC(upload(ctx, h, v, DType::BF16));
-  return upsplit(ctx, f, v);
-}
-
-int finalize(mmpfn_ctx* ctx) {
+// ---- finalize: the host weights of ctx->d packed into a fresh ModelWeights, part by part.  Every fill names the forms
+//      it uploads; their matrix order is the packing function in its argument (none: natural [N][K]).
+int finalize_layers(mmpfn_ctx* ctx, ModelWeights& w) {
   const mmpfn_model_desc& d = ctx->d;
-  const int E = d.emsize, HD = E, Fh = d.nhid, nf = d.encoder_features;
-  ctx->layers.clear();  // a re-finalised context frees the previous model's per-layer buffers and split planes
-  ctx->split.clear();
-  ctx->layers.resize(d.nlayers);
+  const int E = d.emsize, HD = E, Fh = d.nhid;
+  w.layers.resize(d.nlayers);
   for (int l = 0; l < d.nlayers; ++l) {
     const std::string p = "transformer_encoder.layers." + std::to_string(l) + ".";
-    LayerW& L = ctx->layers[l];
+    LayerW& L = w.layers[l];
     GETW(fq, p + "self_attn_between_features._w_qkv", (size_t)3 * HD * E);
     GETW(fo, p + "self_attn_between_features._w_out", (size_t)HD * E);
     GETW(io, p + "self_attn_between_items._w_out", (size_t)HD * E);
     GETW(m1, p + "mlp.linear1.weight", (size_t)Fh * E);
     GETW(m2, p + "mlp.linear2.weight", (size_t)E * Fh);
-    RC(up2(ctx, L.feat_qkv, L.feat_qkv_h, *fq));
-    RC(up2(ctx, L.feat_out, L.feat_out_h, transpose_out(*fo, HD, E)));
-    RC(upload(ctx, L.feat_pack_h, pack_feat_rows(*fq, transpose_out(*fo, HD, E), d.nhead, E), DType::BF16));
-    RC(upload(ctx, L.feat_pack_f, pack_feat_rows(*fq, transpose_out(*fo, HD, E), d.nhead, E, true), DType::F16));
-    RC(upload(ctx, L.item_out_f, permute_rows_f16(transpose_out(*io, HD, E), E, HD), DType::F16));
-    RC(upload(ctx, L.mlp1_f, *m1, DType::F16));
-    RC(upload(ctx, L.mlp2_f, permute_rows_f16(pack_mlp2_perm(*m2, E, Fh), E, Fh), DType::F16));
-    RC(up2(ctx, L.item_out, L.item_out_h, transpose_out(*io, HD, E)));
-    RC(upload(ctx, L.mlp1, *m1));
-    RC(upsplit(ctx, L.mlp1, *m1));
-    RC(upload(ctx, L.mlp1_h, pack_mlp1_perm(*m1, E, Fh), DType::BF16));
-    RC(upload(ctx, L.mlp2, *m2));
-    RC(upsplit(ctx, L.mlp2, *m2));
-    RC(upload(ctx, L.mlp2_h, pack_mlp2_perm(*m2, E, Fh), DType::BF16));
-    RC(upsplit(ctx, L.mlp2_h, pack_mlp2_perm(*m2, E, Fh)));  // parity mode (mlp_x3_kernel)
+    const std::vector<float> fo_t = transpose_out(*fo, HD, E), io_t = transpose_out(*io, HD, E);
+    const std::vector<float> m2p = pack_mlp2_perm(*m2, E, Fh);
+    RC(fill(ctx, L.feat_qkv, *fq, Weight::GEMM));
+    RC(fill(ctx, L.feat_out, fo_t, Weight::GEMM));
+    RC(fill(ctx, L.feat_pack, pack_feat_rows(*fq, fo_t, d.nhead, E), Weight::BF16));
+    RC(fill(ctx, L.feat_pack, pack_feat_rows(*fq, fo_t, d.nhead, E, true), Weight::F16));
+    RC(fill(ctx, L.item_out, io_t, Weight::GEMM));
+    RC(fill(ctx, L.item_out, permute_rows_f16(io_t, E, HD), Weight::F16));
+    RC(fill(ctx, L.mlp1, *m1, Weight::F32 | Weight::F16 | Weight::SPLIT));
+    RC(fill(ctx, L.mlp1, pack_mlp1_perm(*m1, E, Fh), Weight::BF16));
+    RC(fill(ctx, L.mlp2, *m2, Weight::F32));
+    RC(fill(ctx, L.mlp2, m2p, Weight::BF16 | Weight::SPLIT));  // (SPLIT: mlp_x3_kernel)
+    RC(fill(ctx, L.mlp2, permute_rows_f16(m2p, E, Fh), Weight::F16));
+    // item attention: q|k|v of the train rows, q of the test rows
     std::vector<float> wtrain((size_t)3 * HD * E), wtest((size_t)HD * E);
     if (d.two_sets_of_queries) {
       GETW(wq, p + "self_attn_between_items._w_q", (size_t)2 * HD * E);
@@ -187,220 +163,149 @@ int finalize(mmpfn_ctx* ctx) {
       wtrain = *wqkv;
       std::copy(wqkv->begin(), wqkv->begin() + (size_t)HD * E, wtest.begin());
     }
-    RC(upload(ctx, L.item_qkv, wtrain));
-    RC(upload(ctx, L.item_qtest, wtest));
-    RC(upsplit(ctx, L.item_qkv, wtrain));
-    RC(upsplit(ctx, L.item_qtest, wtest));
-    // bf16 copies: the Q rows carry the attention kernel's log2(e)/sqrt(32) (attn_pipe_kernel with
-    // q_prescaled: no per-query scaling pass; one bf16 rounding of Q instead of two)
-    const float qsc = 1.4426950408889634f / std::sqrt((float)(E / d.nhead));
-    for (size_t i = 0; i < (size_t)HD * E; ++i) wtrain[i] *= qsc;
-    for (float& w : wtest) w *= qsc;
-    RC(upload(ctx, L.item_qkv_h, wtrain, DType::BF16));
-    RC(upload(ctx, L.item_qtest_h, wtest, DType::BF16));
-    RC(upload(ctx, L.item_qkv_f, wtrain, DType::F16));
-    RC(upload(ctx, L.item_qtest_f, wtest, DType::F16));
+    RC(fill(ctx, L.item_qkv, wtrain, Weight::F32 | Weight::SPLIT));
+    RC(fill(ctx, L.item_qtest, wtest, Weight::F32 | Weight::SPLIT));
+    prescale_item_q(wtrain, (size_t)HD * E, E / d.nhead);  // the 16-bit forms: prescaled Q rows
+    prescale_item_q(wtest, wtest.size(), E / d.nhead);
+    RC(fill(ctx, L.item_qkv, wtrain, Weight::BF16 | Weight::F16));
+    RC(fill(ctx, L.item_qtest, wtest, Weight::BF16 | Weight::F16));
   }
-  {
-    const std::string en = d.remove_duplicate_features ? "encoder.6.layer.weight" : "encoder.5.layer.weight";
-    GETW(w, en, (size_t)E * 2 * nf);
-    RC(upload(ctx, ctx->enc_w, *w));
-    GETW(yw, "y_encoder.2.layer.weight", (size_t)E * 2);
-    GETW(yb, "y_encoder.2.layer.bias", (size_t)E);
-    RC(upload(ctx, ctx->y_w, *yw));
-    RC(upload(ctx, ctx->y_b, *yb));
-    GETW(pw, "feature_positional_embedding_embeddings.weight", (size_t)E * (E / 4));
-    GETW(pb, "feature_positional_embedding_embeddings.bias", (size_t)E);
-    RC(upload(ctx, ctx->pe_w, *pw));
-    RC(upload(ctx, ctx->pe_b, *pb));
-    GETW(dw1, "decoder_dict.standard.0.weight", (size_t)Fh * E);
-    GETW(db1, "decoder_dict.standard.0.bias", (size_t)Fh);
-    GETW(dw2, "decoder_dict.standard.2.weight", (size_t)d.n_out * Fh);
-    GETW(db2, "decoder_dict.standard.2.bias", (size_t)d.n_out);
-    RC(upload(ctx, ctx->dec_w1, transpose_out(*dw1, Fh, E)));  // [E][Fh]
-    RC(upload(ctx, ctx->dec_b1, *db1));
-    RC(upload(ctx, ctx->dec_w2, *dw2));
-    RC(upload(ctx, ctx->dec_b2, *db2));
-    if (d.n_out <= 16 && Fh % 128 == 0) {
-      std::vector<float> w2p((size_t)16 * Fh, 0.f);
-      std::copy(dw2->begin(), dw2->end(), w2p.begin());
-      w2p = pack_mlp2_perm(w2p, 16, Fh);
-      RC(upload(ctx, ctx->dec_w1_h, *dw1, DType::BF16));
-      RC(upload(ctx, ctx->dec_w1_f, *dw1, DType::F16));
-      RC(upload(ctx, ctx->dec_w2p_h, w2p, DType::BF16));
-      RC(upload(ctx, ctx->dec_w2p_f, w2p, DType::F16));
-    }
-  }
-  const int D = d.nhid;
-  if (d.mixer_type == MMPFN_MIXER_MGM || d.mixer_type == MMPFN_MIXER_MGM_CAP) {
-    const int mg = d.mgm_heads;
-    std::vector<float> W1((size_t)mg * D * D), B1((size_t)mg * D), W2((size_t)mg * E * (D / 2)),
-        B2((size_t)mg * E);
-    for (int h = 0; h < mg; ++h) {
-      const std::string p = "mgm.projs." + std::to_string(h) + ".";
-      GETW(g, p + "0.weight", (size_t)D);
-      GETW(b, p + "0.bias", (size_t)D);
-      GETW(w1, p + "1.weight", (size_t)D * D);
-      GETW(b1, p + "1.bias", (size_t)D);
-      GETW(w2, p + "4.weight", (size_t)E * (D / 2));
-      GETW(b2, p + "4.bias", (size_t)E);
-      std::vector<float> w = *w1, c = *b1;
-      fold_ln(w, c, g->data(), b->data(), D, D);
-      // interleave GLU halves in 16-row blocks: [a 16i..16i+15 | b 16i..16i+15] per 32 rows
-      for (int i = 0; i < D / 32; ++i)
-        for (int r = 0; r < 32; ++r) {
-          const int src = r < 16 ? 16 * i + r : D / 2 + 16 * i + (r - 16);
-          const size_t dst = (size_t)h * D + 32 * i + r;
-          std::memcpy(&W1[dst * D], &w[(size_t)src * D], D * sizeof(float));
-          B1[dst] = c[src];
-        }
-      std::copy(w2->begin(), w2->end(), W2.begin() + (size_t)h * E * (D / 2));
-      std::copy(b2->begin(), b2->end(), B2.begin() + (size_t)h * E);
-    }
-    RC(up2(ctx, ctx->mgm_w1, ctx->mgm_w1_h, W1));
-    RC(upload(ctx, ctx->mgm_b1, B1));
-    RC(up2(ctx, ctx->mgm_w2, ctx->mgm_w2_h, W2));
-    if (mgm_f16_shape(d)) {  // PREC_F16's head bank (the big-tile kernels only)
-      RC(upload(ctx, ctx->mgm_w1_f, W1, DType::F16));
-      RC(upload(ctx, ctx->mgm_w2_f, W2, DType::F16));
-    } else {  // a re-finalised context with another head count must not keep the previous model's fp16 bank
-      ctx->mgm_w1_f.reset();
-      ctx->mgm_w2_f.reset();
-    }
-    RC(upload(ctx, ctx->mgm_b2, B2));
-  }
-  if (d.mixer_type == MMPFN_MIXER_MGM_CAP) {
-    const int cap = d.cap_heads;
-    GETW(qs, "cap.queries", (size_t)cap * E);
-    GETW(qpw, "cap.q_proj.weight", (size_t)E * E);
-    GETW(inw, "cap.mha.in_proj_weight", (size_t)3 * E * E);
-    GETW(inb, "cap.mha.in_proj_bias", (size_t)3 * E);
-    GETW(ow, "cap.mha.out_proj.weight", (size_t)E * E);
-    GETW(ob, "cap.mha.out_proj.bias", (size_t)E);
-    GETW(kg, "cap.k_norm.weight", (size_t)E);
-    GETW(kb, "cap.k_norm.bias", (size_t)E);
-    GETW(qg, "cap.q_norm.weight", (size_t)E);
-    GETW(qb, "cap.q_norm.bias", (size_t)E);
-    GETW(ng, "cap.out_norm.weight", (size_t)E);
-    GETW(nb, "cap.out_norm.bias", (size_t)E);
-    GETW(f0w, "cap.ffn.0.weight", (size_t)2 * E * E);
-    GETW(f0b, "cap.ffn.0.bias", (size_t)2 * E);
-    GETW(f3w, "cap.ffn.3.weight", (size_t)2 * E * E);
-    GETW(f3b, "cap.ffn.3.bias", (size_t)E);
-    // weight-only query path: in_proj_q(q_proj(q_norm(queries)))  (transformer.py:81)
-    std::vector<float> qp((size_t)cap * E);
-    for (int c = 0; c < cap; ++c) {
-      const float* q = qs->data() + (size_t)c * E;
-      double mu = 0, var = 0;
-      for (int e = 0; e < E; ++e) mu += q[e];
-      mu /= E;
-      for (int e = 0; e < E; ++e) var += (q[e] - mu) * (q[e] - mu);
-      var /= E;
-      const double inv = 1.0 / std::sqrt(var + d.ln_eps);
-      std::vector<double> qn(E), qq(E);
-      for (int e = 0; e < E; ++e) qn[e] = (q[e] - mu) * inv * (*qg)[e] + (*qb)[e];
-      for (int o = 0; o < E; ++o) {
-        double a = 0;
-        for (int e = 0; e < E; ++e) a += (*qpw)[(size_t)o * E + e] * qn[e];
-        qq[o] = a;
-      }
-      for (int o = 0; o < E; ++o) {
-        double a = (*inb)[o];
-        for (int e = 0; e < E; ++e) a += (*inw)[(size_t)o * E + e] * qq[e];
-        qp[(size_t)c * E + o] = (float)a;
-      }
-    }
-    RC(upload(ctx, ctx->cap_qp, qp));
-    // K/V in-projection with k_norm's affine folded in (k = v = k_norm(src))
-    std::vector<float> wkv(inw->begin() + (size_t)E * E, inw->end());
-    std::vector<float> bkv(inb->begin() + E, inb->end());
-    fold_ln(wkv, bkv, kg->data(), kb->data(), 2 * E, E);
-    RC(up2(ctx, ctx->cap_kv, ctx->cap_kv_h, wkv));
-    RC(upload(ctx, ctx->cap_kv_b, bkv));
-    RC(up2(ctx, ctx->cap_o, ctx->cap_o_h, *ow));
-    RC(upload(ctx, ctx->cap_o_b, *ob));
-    RC(up2(ctx, ctx->cap_f0, ctx->cap_f0_h, *f0w));
-    RC(upload(ctx, ctx->cap_f0_b, *f0b));
-    RC(up2(ctx, ctx->cap_f3, ctx->cap_f3_h, *f3w));
-    RC(upload(ctx, ctx->cap_f3_b, *f3b));
-    RC(upload(ctx, ctx->cap_ng, *ng));
-    RC(upload(ctx, ctx->cap_nb, *nb));
-    // the 16-bit modes' tail runs on mlp_rows_kernel's CAP form
-    RC(upload(ctx, ctx->cap_f0_p, pack_mlp1_perm(*f0w, E, 2 * E), DType::BF16));
-    RC(upload(ctx, ctx->cap_f3_p, pack_mlp2_perm(*f3w, E, 2 * E), DType::BF16));
-    std::vector<float> v;  // [bo | b0 | g | b + b3]
-    for (const std::vector<float>* part : {ob, f0b, ng}) v.insert(v.end(), part->begin(), part->end());
-    for (int e = 0; e < E; ++e) v.push_back((*nb)[e] + (*f3b)[e]);
-    RC(upload(ctx, ctx->cap_vecs, v));
-  }
-  if (d.mixer_type == MMPFN_MIXER_MOE) {
-    const int ne = d.mgm_heads;
-    std::vector<float> W1((size_t)ne * (D / 2) * D), B1((size_t)ne * (D / 2)), W2((size_t)ne * E * (D / 2)),
-        B2((size_t)ne * E);
-    for (int i = 0; i < ne; ++i) {
-      const std::string p = "moe.experts." + std::to_string(i) + ".";
-      GETW(g, p + "0.weight", (size_t)D);
-      GETW(b, p + "0.bias", (size_t)D);
-      GETW(w1, p + "1.weight", (size_t)(D / 2) * D);
-      GETW(b1, p + "1.bias", (size_t)D / 2);
-      GETW(w2, p + "4.weight", (size_t)E * (D / 2));
-      GETW(b2, p + "4.bias", (size_t)E);
-      std::vector<float> w = *w1, c = *b1;
-      fold_ln(w, c, g->data(), b->data(), D / 2, D);
-      std::copy(w.begin(), w.end(), W1.begin() + (size_t)i * (D / 2) * D);
-      std::copy(c.begin(), c.end(), B1.begin() + (size_t)i * (D / 2));
-      std::copy(w2->begin(), w2->end(), W2.begin() + (size_t)i * E * (D / 2));
-      std::copy(b2->begin(), b2->end(), B2.begin() + (size_t)i * E);
-    }
-    GETW(gw, "moe.gate.weight", (size_t)ne * D);
-    GETW(gb, "moe.gate.bias", (size_t)ne);
-    RC(up2(ctx, ctx->moe_w1, ctx->moe_w1_h, W1));
-    RC(upload(ctx, ctx->moe_b1, B1));
-    RC(up2(ctx, ctx->moe_w2, ctx->moe_w2_h, W2));
-    RC(upload(ctx, ctx->moe_b2, B2));
-    RC(upload(ctx, ctx->moe_gw, *gw));
-    RC(upload(ctx, ctx->moe_gb, *gb));
-  }
-  HIPCHK(hipDeviceSynchronize());
   return MMPFN_OK;
 }
 
-// weight operand of launch_gemm in a precision mode: bf16 copy, fp32 copy (PREC_F32_MFMA), or the
-// hi | lo planes of the parity mode with the offset of the lo plane
-void setw(const mmpfn_ctx* ctx, GemmArgs& a, const DevBuf& f, const DevBuf& h, int prec) {
-  a.w_lo_off = 0;
-  if (prec == PREC_BF16) {
-    a.W = h.p;
-  } else if (prec == PREC_F32) {
-    const auto it = ctx->split.find(f.p);
-    a.W = it == ctx->split.end() ? nullptr : it->second.p;
-    a.w_lo_off = it == ctx->split.end() ? 0 : (int64_t)it->second.n;
-  } else {
-    a.W = f.p;
+int finalize_encoders_decoder(mmpfn_ctx* ctx, ModelWeights& w) {
+  const mmpfn_model_desc& d = ctx->d;
+  const int E = d.emsize, Fh = d.nhid, nf = d.encoder_features;
+  GETW(ew, d.remove_duplicate_features ? "encoder.6.layer.weight" : "encoder.5.layer.weight", (size_t)E * 2 * nf);
+  GETW(yw, "y_encoder.2.layer.weight", (size_t)E * 2);
+  GETW(yb, "y_encoder.2.layer.bias", (size_t)E);
+  GETW(pw, "feature_positional_embedding_embeddings.weight", (size_t)E * (E / 4));
+  GETW(pb, "feature_positional_embedding_embeddings.bias", (size_t)E);
+  GETW(dw1, "decoder_dict.standard.0.weight", (size_t)Fh * E);
+  GETW(db1, "decoder_dict.standard.0.bias", (size_t)Fh);
+  GETW(dw2, "decoder_dict.standard.2.weight", (size_t)d.n_out * Fh);
+  GETW(db2, "decoder_dict.standard.2.bias", (size_t)d.n_out);
+  for (auto [buf, v] : {std::pair{&w.enc_w, ew}, {&w.y_w, yw}, {&w.y_b, yb}, {&w.pe_w, pw}, {&w.pe_b, pb},
+                        {&w.dec_b1, db1}, {&w.dec_b2, db2}})
+    RC(upload(ctx, *buf, *v));
+  RC(fill(ctx, w.dec_w1, transpose_out(*dw1, Fh, E), Weight::F32));  // launch_decoder: W1 [E][Fh], W2 natural
+  RC(fill(ctx, w.dec_w2, *dw2, Weight::F32));
+  if (d.n_out <= 16 && Fh % 128 == 0) {  // launch_decoder_mfma: W1 natural, W2 zero-padded to [16][Fh] and permuted
+    std::vector<float> w2p((size_t)16 * Fh, 0.f);
+    std::copy(dw2->begin(), dw2->end(), w2p.begin());
+    RC(fill(ctx, w.dec_w1, *dw1, Weight::BF16 | Weight::F16));
+    RC(fill(ctx, w.dec_w2, pack_mlp2_perm(w2p, 16, Fh), Weight::BF16 | Weight::F16));
   }
+  return MMPFN_OK;
 }
 
-// parity-mode row-resident projections (rowgemm3.hip) on the split weights
-Proj3Set p3set(const mmpfn_ctx* ctx, const DevBuf& f, const float* A, int64_t rdiv, int64_t rmul, int64_t rmul2,
-               int64_t roff, int64_t M, int N) {
-  const auto it = ctx->split.find(f.p);
-  Proj3Set s{A, rdiv, rmul, rmul2, roff, nullptr, 0, (int)M, N};
-  if (it != ctx->split.end()) s.W = it->second.p, s.w_lo = (int64_t)it->second.n;
-  return s;
+// the MGM head bank (glu) or the MoE experts, heads stacked, every form in the one order: W1 [n][N1][D] with the
+// LayerNorm folded in -- MGM: N1 = D, the GLU halves interleaved (glu_interleave); MoE: N1 = D/2 -- and W2 [n][E][D/2]
+int finalize_heads(mmpfn_ctx* ctx, HeadBank& hb, const std::string& prefix, bool glu) {
+  const mmpfn_model_desc& d = ctx->d;
+  const int E = d.emsize, D = d.nhid, n = d.mgm_heads, N1 = glu ? D : D / 2;
+  std::vector<float> W1((size_t)n * N1 * D), B1((size_t)n * N1), W2((size_t)n * E * (D / 2)), B2((size_t)n * E);
+  for (int h = 0; h < n; ++h) {
+    const std::string p = prefix + std::to_string(h) + ".";
+    GETW(g, p + "0.weight", (size_t)D);
+    GETW(b, p + "0.bias", (size_t)D);
+    GETW(w1, p + "1.weight", (size_t)N1 * D);
+    GETW(b1, p + "1.bias", (size_t)N1);
+    GETW(w2, p + "4.weight", (size_t)E * (D / 2));
+    GETW(b2, p + "4.bias", (size_t)E);
+    std::vector<float> wf = *w1, c = *b1;
+    fold_ln(wf, c, g->data(), b->data(), N1, D);
+    if (glu) glu_interleave(wf, c, D);
+    std::copy(wf.begin(), wf.end(), W1.begin() + (size_t)h * N1 * D);
+    std::copy(c.begin(), c.end(), B1.begin() + (size_t)h * N1);
+    std::copy(w2->begin(), w2->end(), W2.begin() + (size_t)h * E * (D / 2));
+    std::copy(b2->begin(), b2->end(), B2.begin() + (size_t)h * E);
+  }
+  // (fp16: PREC_F16's MGM head bank, the big-tile kernels only)
+  const unsigned forms = glu && mgm_f16_shape(d) ? Weight::GEMM | Weight::F16 : Weight::GEMM;
+  RC(fill(ctx, hb.w1, W1, forms));
+  RC(fill(ctx, hb.w2, W2, forms));
+  RC(upload(ctx, hb.b1, B1));
+  return upload(ctx, hb.b2, B2);
 }
-hipError_t p3_resln(const mmpfn_ctx* ctx, const DevBuf& f, const void* O, int64_t M, float* X, hipStream_t st) {
-  const Proj3Set s = p3set(ctx, f, (const float*)O, 1, 1, 0, 0, M, 192);
-  return launch_proj3_resln(s.A, s.W, s.w_lo, M, X, ctx->d.ln_eps, st);
+
+int finalize_cap(mmpfn_ctx* ctx, ModelWeights& w) {
+  const mmpfn_model_desc& d = ctx->d;
+  const int E = d.emsize, cap = d.cap_heads;
+  GETW(qs, "cap.queries", (size_t)cap * E);
+  GETW(qpw, "cap.q_proj.weight", (size_t)E * E);
+  GETW(inw, "cap.mha.in_proj_weight", (size_t)3 * E * E);
+  GETW(inb, "cap.mha.in_proj_bias", (size_t)3 * E);
+  GETW(ow, "cap.mha.out_proj.weight", (size_t)E * E);
+  GETW(ob, "cap.mha.out_proj.bias", (size_t)E);
+  GETW(kg, "cap.k_norm.weight", (size_t)E);
+  GETW(kb, "cap.k_norm.bias", (size_t)E);
+  GETW(qg, "cap.q_norm.weight", (size_t)E);
+  GETW(qb, "cap.q_norm.bias", (size_t)E);
+  GETW(ng, "cap.out_norm.weight", (size_t)E);
+  GETW(nb, "cap.out_norm.bias", (size_t)E);
+  GETW(f0w, "cap.ffn.0.weight", (size_t)2 * E * E);
+  GETW(f0b, "cap.ffn.0.bias", (size_t)2 * E);
+  GETW(f3w, "cap.ffn.3.weight", (size_t)2 * E * E);
+  GETW(f3b, "cap.ffn.3.bias", (size_t)E);
+  RC(upload(ctx, w.cap_qp, cap_query_path(qs->data(), qg->data(), qb->data(), qpw->data(), inw->data(), inb->data(),
+                                          cap, E, d.ln_eps)));
+  // K/V in-projection with k_norm's affine folded in (k = v = k_norm(src))
+  std::vector<float> wkv(inw->begin() + (size_t)E * E, inw->end());
+  std::vector<float> bkv(inb->begin() + E, inb->end());
+  fold_ln(wkv, bkv, kg->data(), kb->data(), 2 * E, E);
+  RC(fill(ctx, w.cap_kv, wkv, Weight::GEMM));
+  RC(fill(ctx, w.cap_o, *ow, Weight::GEMM));
+  // the FFN's bf16 forms are read by the 16-bit modes' tail alone (launch_cap_tail: mlp_rows_kernel's CAP form)
+  RC(fill(ctx, w.cap_f0, *f0w, Weight::F32 | Weight::SPLIT));
+  RC(fill(ctx, w.cap_f0, pack_mlp1_perm(*f0w, E, 2 * E), Weight::BF16));
+  RC(fill(ctx, w.cap_f3, *f3w, Weight::F32 | Weight::SPLIT));
+  RC(fill(ctx, w.cap_f3, pack_mlp2_perm(*f3w, E, 2 * E), Weight::BF16));
+  std::vector<float> v;  // [bo | b0 | g | b + b3]
+  for (const std::vector<float>* part : {ob, f0b, ng}) v.insert(v.end(), part->begin(), part->end());
+  for (int e = 0; e < E; ++e) v.push_back((*nb)[e] + (*f3b)[e]);
+  RC(upload(ctx, w.cap_vecs, v));
+  RC(upload(ctx, w.cap_kv_b, bkv));
+  for (auto [buf, b] : {std::pair{&w.cap_o_b, ob}, {&w.cap_f0_b, f0b}, {&w.cap_f3_b, f3b}, {&w.cap_ng, ng},
+                        {&w.cap_nb, nb}})
+    RC(upload(ctx, *buf, *b));
+  return MMPFN_OK;
+}
+
+int finalize(mmpfn_ctx* ctx) {
+  const mmpfn_model_desc& d = ctx->d;
+  ctx->w = ModelWeights();  // the previous model's set goes first: a re-finalise never holds two sets on the device
+  ModelWeights w;
+  RC(finalize_layers(ctx, w));
+  RC(finalize_encoders_decoder(ctx, w));
+  if (d.mixer_type == MMPFN_MIXER_MGM || d.mixer_type == MMPFN_MIXER_MGM_CAP)
+    RC(finalize_heads(ctx, w.mgm, "mgm.projs.", true));
+  if (d.mixer_type == MMPFN_MIXER_MGM_CAP) RC(finalize_cap(ctx, w));
+  if (d.mixer_type == MMPFN_MIXER_MOE) {
+    RC(finalize_heads(ctx, w.moe, "moe.experts.", false));
+    GETW(gw, "moe.gate.weight", (size_t)d.mgm_heads * d.nhid);
+    GETW(gb, "moe.gate.bias", (size_t)d.mgm_heads);
+    RC(upload(ctx, w.moe_gw, *gw));
+    RC(upload(ctx, w.moe_gb, *gb));
+  }
+  HIPCHK(hipDeviceSynchronize());
+  ctx->w = std::move(w);
+  return MMPFN_OK;
+}
+
+// parity-mode row-resident projections (rowgemm3.hip) on the split planes of w
+Proj3Set p3set(const Weight& w, const float* A, int64_t rdiv, int64_t rmul, int64_t rmul2, int64_t roff, int64_t M,
+               int N) {
+  return Proj3Set{A, rdiv, rmul, rmul2, roff, w.split.p, w.numel, (int)M, N};
+}
+hipError_t p3_resln(const mmpfn_ctx* ctx, const Weight& w, const void* O, int64_t M, float* X, hipStream_t st) {
+  return launch_proj3_resln((const float*)O, w.split.p, w.numel, M, X, ctx->d.ln_eps, st);
 }
 
 GemmArgs gargs() {
   GemmArgs a;
   std::memset(&a, 0, sizeof(a));
-  a.a_rdiv = 1ll << 62;
-  a.a_rmul = 0;
-  a.a_rmul2 = 1;
-  a.rdiv2 = 1ll << 62;
-  a.ln_eps = 1e-5f;
+  a.a_rdiv = a.rdiv2 = 1ll << 62, a.a_rmul2 = 1, a.ln_eps = 1e-5f;
   return a;
 }
 
@@ -414,8 +319,10 @@ struct PrecMode {
   int f8 = 0;           // the fp8 P.V variant of the item attention (0: none)
   bool is16() const { return prec16(base); }
   bool f16() const { return base == PREC_F16; }
-  // PREC_F16 runs the bf16 mode's kernels in their F16 forms: launch_gemm, launch_attn and setw see PREC_BF16
+  // PREC_F16 runs the bf16 mode's kernels in their F16 forms: launch_gemm, launch_attn and Weight::gemm_operand see
+  // PREC_BF16
   int gemm() const { return is16() ? PREC_BF16 : base; }
+  DType w16() const { return f16() ? DType::F16 : DType::BF16; }  // the 16-bit modes' weight form (Weight::op16)
   // the inter-kernel state X: fp32, or fp16 under PREC_F16 (then the attention output O too)
   DType state() const { return f16() ? DType::F16 : DType::F32; }
   int state_bytes() const { return f16() ? 2 : 4; }
@@ -432,6 +339,17 @@ PrecMode decode_prec(int code, int T) {
   return m;
 }
 PrecMode lane_prec(const Lane& l) { return PrecMode{l.prec, l.f8}; }
+
+// the selected lane's workspaces for M members of S x T tokens with Npad padded train rows: ws_X (own_state; a tap
+// runs on the caller's) and ws_O hold the state and the attention output, ws_big the Q / K / V^T of the feature
+// attention (member by member) or of the item attention (all members at once)
+int lane_workspace(mmpfn_ctx* ctx, int S, int T, int Npad, int M, bool own_state) {
+  const size_t E = ctx->d.emsize, R = (size_t)S * T, Tpad = (T + 63) / 64 * 64;
+  const size_t feat = R * E + (size_t)2 * S * Tpad * E, item = (size_t)M * (R * E + (size_t)2 * T * Npad * E);
+  if (own_state) RC(ensure(ctx, ctx->ws_X, (size_t)M * R * E * 4));
+  RC(ensure(ctx, ctx->ws_O, (size_t)M * R * E * 4));
+  return ensure(ctx, ctx->ws_big, std::max(feat, item) * 4);
+}
 
 // member m (of M, all of the geometry set by member 0) -> X[m] = embedded input [T][S][E]
 int embed(mmpfn_ctx* ctx, const float* x, int S, int F, const float* tokens, int C, const float* y, int N,
@@ -453,17 +371,13 @@ int embed(mmpfn_ctx* ctx, const float* x, int S, int F, const float* tokens, int
   if (m == 0) {
     ctx->S = S, ctx->T = T, ctx->N = N, ctx->G = G, ctx->C = C, ctx->Npad = Npad, ctx->prec = pm.base, ctx->M = M;
     ctx->f8 = pm.f8;
-    RC(ensure(ctx, ctx->ws_X, (size_t)M * R * E * 4));
-    RC(ensure(ctx, ctx->ws_O, (size_t)M * R * E * 4));
-    const size_t Tpad = (T + 63) / 64 * 64;
-    const size_t big = std::max(R * E + (size_t)2 * S * Tpad * E, (size_t)M * (R * E + (size_t)2 * T * Npad * E)) * 4;
-    RC(ensure(ctx, ctx->ws_big, big));
+    RC(lane_workspace(ctx, S, T, Npad, M, true));
     RC(ensure(ctx, ctx->ws_pe, (size_t)(G + C + 1) * E * 4));
     RC(ensure(ctx, ctx->ws_slots, (size_t)(G + 1) * fpg * sizeof(SlotParams)));
     RC(ensure(ctx, ctx->ws_scr, 256));
     RC(ensure_flag(ctx, ctx->ws_flag, st));
     flag = (int*)ctx->ws_flag.p;
-    HIPCHK(launch_pos_emb(pos_rand, G + C, (const float*)ctx->pe_w.p, (const float*)ctx->pe_b.p,
+    HIPCHK(launch_pos_emb(pos_rand, G + C, (const float*)ctx->w.pe_w.p, (const float*)ctx->w.pe_b.p,
                           (float*)ctx->ws_pe.p, E, st));
   } else {
     if (S != ctx->S || T != ctx->T || N != ctx->N || G != ctx->G || C != ctx->C || pm.base != ctx->prec ||
@@ -476,9 +390,9 @@ int embed(mmpfn_ctx* ctx, const float* x, int S, int F, const float* tokens, int
   HIPCHK(launch_encode_stats(x, S, F, N, G, fpg, d.outlier_sigma, (SlotParams*)ctx->ws_slots.p, y, N,
                              (float*)ctx->ws_scr.p, st));
   HIPCHK(launch_assemble(x, S, F, G, fpg, d.encoder_features, (const SlotParams*)ctx->ws_slots.p,
-                         (const float*)ctx->enc_w.p, (const float*)ctx->ws_pe.p, tokens, C, y, N, uniq, U,
-                         (const float*)ctx->y_w.p, (const float*)ctx->y_b.p, (const float*)ctx->ws_scr.p, X, pm.state(),
-                         E, flag, st));
+                         (const float*)ctx->w.enc_w.p, (const float*)ctx->ws_pe.p, tokens, C, y, N, uniq, U,
+                         (const float*)ctx->w.y_w.p, (const float*)ctx->w.y_b.p, (const float*)ctx->ws_scr.p, X,
+                         pm.state(), E, flag, st));
   ctx->embedded = true;
   return MMPFN_OK;
 }
@@ -492,19 +406,15 @@ int embed_cached(mmpfn_ctx* ctx, const mmpfn_cache* cc, const float* x, int S, i
   if (S <= 0 || F != cc->F || C != cc->C || (F > 0 && !x) || (C > 0 && !tokens))
     return fail(ctx, MMPFN_ERR_INVALID, "test rows must match the cache's features, tokens and precision");
   const int E = d.emsize, fpg = d.features_per_group, G = cc->G, T = cc->T;
-  const size_t R = (size_t)S * T;
   hipStream_t st = ctx->stream;
   ctx->S = S, ctx->T = T, ctx->N = 0, ctx->G = G, ctx->C = C, ctx->Npad = 0, ctx->prec = cc->prec, ctx->M = 1;
   ctx->f8 = 0;  // the cache keeps bf16 V^T: its test rows run the bf16 P.V
-  RC(ensure(ctx, ctx->ws_X, R * E * 4));
-  RC(ensure(ctx, ctx->ws_O, R * E * 4));
-  const size_t Tpad = (T + 63) / 64 * 64;
-  RC(ensure(ctx, ctx->ws_big, (R * E + (size_t)2 * S * Tpad * E) * 4));
+  RC(lane_workspace(ctx, S, T, 0, 1, true));
   RC(ensure_flag(ctx, ctx->ws_flag, st));
   int* flag = (int*)ctx->ws_flag.p;
   HIPCHK(launch_assemble(x, S, F, G, fpg, d.encoder_features, (const SlotParams*)cc->slots.p,
-                         (const float*)ctx->enc_w.p, (const float*)cc->pe.p, tokens, C, nullptr, 0,
-                         (const float*)cc->uniq.p, cc->U, (const float*)ctx->y_w.p, (const float*)ctx->y_b.p,
+                         (const float*)ctx->w.enc_w.p, (const float*)cc->pe.p, tokens, C, nullptr, 0,
+                         (const float*)cc->uniq.p, cc->U, (const float*)ctx->w.y_w.p, (const float*)ctx->w.y_b.p,
                          (const float*)cc->ymean.p, ctx->ws_X.p, lane_prec(*ctx).state(), E, flag, st));
   ctx->embedded = true;
   return MMPFN_OK;
@@ -525,7 +435,7 @@ int feat_sublayer(mmpfn_ctx* ctx, const LayerW& L, void* Xv, int S, int T, int M
   if (b16 && T <= 64) {
     // one wave per row (all M members' rows in one launch), the whole sublayer in registers (featrow.hip); an
     // fp16 state always comes here (decode_prec keeps PREC_F16 to T <= 64)
-    HIPCHK(launch_feat_rows(Xv, pm.f16() ? L.feat_pack_f.p : L.feat_pack_h.p, S, T, M, E, H, d.ln_eps, st, pm.state(),
+    HIPCHK(launch_feat_rows(Xv, L.feat_pack.op16(pm.w16()), S, T, M, E, H, d.ln_eps, st, pm.state(),
                             last));
     return MMPFN_OK;
   }
@@ -538,12 +448,12 @@ int feat_sublayer(mmpfn_ctx* ctx, const LayerW& L, void* Xv, int S, int T, int M
     void* Vf = (unsigned char*)Kf + (size_t)S * H * Tpad * 32 * eb;
     // logical rows m = s*T + t: A row t*S + s; scatter batch b = s, position t
     if (pm.base == PREC_F32) {
-      const Proj3Set ps = p3set(ctx, L.feat_qkv, X, T, 1, S, 0, R, 3 * E);
+      const Proj3Set ps = p3set(L.feat_qkv, X, T, 1, S, 0, R, 3 * E);
       HIPCHK(launch_proj3_qkv(&ps, 1, Qf, Kf, Vf, T, Tpad, H, st));
     } else {
       GemmArgs a = gargs();
       a.A = X, a.lda = E, a.a_rdiv = T, a.a_rmul = 1, a.a_rmul2 = S;
-      setw(ctx, a, L.feat_qkv, L.feat_qkv_h, pm.gemm());
+      L.feat_qkv.gemm_operand(a, pm.gemm());
       a.M = (int)R, a.N = 3 * E, a.K = E;
       a.q = Qf, a.k = Kf, a.v = Vf, a.S = T, a.Npad = Tpad, a.T = T, a.H = H;
       HIPCHK(launch_gemm(a, pm.gemm(), EPI_ITEM_QKV, true, !b16, 1, st));
@@ -560,7 +470,7 @@ int feat_sublayer(mmpfn_ctx* ctx, const LayerW& L, void* Xv, int S, int T, int M
       continue;
     }
     GemmArgs b = gargs();
-    b.A = O, b.lda = E, setw(ctx, b, L.feat_out, L.feat_out_h, pm.gemm());
+    b.A = O, b.lda = E, L.feat_out.gemm_operand(b, pm.gemm());
     b.M = (int)R, b.N = E, b.K = E, b.X = X, b.ln_eps = d.ln_eps;
     HIPCHK(launch_gemm(b, pm.gemm(), EPI_RES_LN, !b16, true, 1, st));
   }
@@ -573,12 +483,12 @@ int item_out_proj(mmpfn_ctx* ctx, const LayerW& L, const void* O, void* Xv, int6
   const int E = d.emsize;
   hipStream_t st = ctx->stream;
   if (pm.is16()) {
-    HIPCHK(launch_rowgemm_resln(O, pm.f16() ? L.item_out_f.p : L.item_out_h.p, RM, Xv, d.ln_eps, st, pm.state()));
+    HIPCHK(launch_rowgemm_resln(O, L.item_out.op16(pm.w16()), RM, Xv, d.ln_eps, st, pm.state()));
   } else if (pm.base == PREC_F32) {
     HIPCHK(p3_resln(ctx, L.item_out, O, RM, (float*)Xv, st));
   } else {
     GemmArgs b = gargs();
-    b.A = O, b.lda = E, setw(ctx, b, L.item_out, L.item_out_h, pm.base);
+    b.A = O, b.lda = E, L.item_out.gemm_operand(b, pm.base);
     b.M = (int)RM, b.N = E, b.K = E, b.X = (float*)Xv, b.ln_eps = d.ln_eps;
     HIPCHK(launch_gemm(b, pm.base, EPI_RES_LN, true, true, 1, st));
   }
@@ -597,7 +507,7 @@ int item_out_proj(mmpfn_ctx* ctx, const LayerW& L, const void* O, void* Xv, int6
 int item_sublayer(mmpfn_ctx* ctx, int l, void* Xv, int S, int T, int N, int Npad, int M, PrecMode pm, bool fuse_out,
                   bool last = false) {
   const mmpfn_model_desc& d = ctx->d;
-  const LayerW& L = ctx->layers[l];
+  const LayerW& L = ctx->w.layers[l];
   const int E = d.emsize, H = d.nhead, Q = S - N;
   const int TM = last ? M : T * M;               // token columns of the batch (attention batches)
   const int64_t RM = (int64_t)S * TM;            // tokens of the batch
@@ -607,7 +517,7 @@ int item_sublayer(mmpfn_ctx* ctx, int l, void* Xv, int S, int T, int N, int Npad
   float* Xall = (float*)Xv;
   // the 16-bit modes run the row-resident projections and the pipelined attention; PREC_F16 in their F16 forms
   // (fp16 X and O, fp16 weight copies)
-  const bool b16 = pm.is16(), h16 = pm.f16();
+  const bool b16 = pm.is16();
   const int eb = pm.op_bytes();
   hipStream_t st = ctx->stream;
   void* O = ctx->ws_O.p;
@@ -622,15 +532,15 @@ int item_sublayer(mmpfn_ctx* ctx, int l, void* Xv, int S, int T, int N, int Npad
     const unsigned char* Kc = (const unsigned char*)cc->kv.p + (size_t)l * 2 * kvl + ccol;
     const unsigned char* Vc = Kc + kvl;
     if (b16) {
-      HIPCHK(launch_rowgemm_qkv(Xv, S, cs, 1, 0, h16 ? L.item_qtest_f.p : L.item_qtest_h.p, TM * S, E, Qi, Ki, Vi, S,
+      HIPCHK(launch_rowgemm_qkv(Xv, S, cs, 1, 0, L.item_qtest.op16(pm.w16()), TM * S, E, Qi, Ki, Vi, S,
                                 Npad, H, st, pm.state(), pm.qk()));
     } else if (pm.base == PREC_F32) {
-      const Proj3Set ps = p3set(ctx, L.item_qtest, Xall, S, cs, 1, 0, (int64_t)TM * S, E);
+      const Proj3Set ps = p3set(L.item_qtest, Xall, S, cs, 1, 0, (int64_t)TM * S, E);
       HIPCHK(launch_proj3_qkv(&ps, 1, Qi, Ki, Vi, S, Npad, H, st));
     } else {
       GemmArgs c = gargs();
       c.A = Xall, c.lda = E, c.a_rdiv = S, c.a_rmul = cs, c.a_roff = 0;
-      setw(ctx, c, L.item_qtest, L.item_qtest_h, pm.base);
+      L.item_qtest.gemm_operand(c, pm.base);
       c.M = TM * S, c.N = E, c.K = E;
       c.q = Qi, c.k = Ki, c.v = Vi, c.S = S, c.Npad = Npad, c.T = TM, c.H = H;
       HIPCHK(launch_gemm(c, pm.base, EPI_ITEM_QKV, true, true, 1, st));
@@ -647,24 +557,24 @@ int item_sublayer(mmpfn_ctx* ctx, int l, void* Xv, int S, int T, int N, int Npad
   } else {
     if (b16) {  // row-resident projections straight into the attention layouts
       // train rows q|k|v and test rows q in one launch (test-row blocks last)
-      HIPCHK(launch_rowgemm_qkv_pair(Xv, N, 0, h16 ? L.item_qkv_f.p : L.item_qkv_h.p, TM * N, 3 * E, Q, N,
-                                     h16 ? L.item_qtest_f.p : L.item_qtest_h.p, TM * Q, E, cs, Qi, Ki, Vi, S, Npad, H, st,
+      HIPCHK(launch_rowgemm_qkv_pair(Xv, N, 0, L.item_qkv.op16(pm.w16()), TM * N, 3 * E, Q, N,
+                                     L.item_qtest.op16(pm.w16()), TM * Q, E, cs, Qi, Ki, Vi, S, Npad, H, st,
                                      pm.state(), pm.qk()));
     } else if (pm.base == PREC_F32) {  // train rows q|k|v and test rows q in one launch
-      const Proj3Set ps[2] = {p3set(ctx, L.item_qkv, Xall, N, cs, 1, 0, (int64_t)TM * N, 3 * E),
-                              p3set(ctx, L.item_qtest, Xall, Q > 0 ? Q : 1, cs, 1, N, (int64_t)TM * Q, E)};
+      const Proj3Set ps[2] = {p3set(L.item_qkv, Xall, N, cs, 1, 0, (int64_t)TM * N, 3 * E),
+                              p3set(L.item_qtest, Xall, Q > 0 ? Q : 1, cs, 1, N, (int64_t)TM * Q, E)};
       HIPCHK(launch_proj3_qkv(ps, 2, Qi, Ki, Vi, S, Npad, H, st));
     } else {
       GemmArgs a = gargs();
       a.A = Xall, a.lda = E, a.a_rdiv = N, a.a_rmul = cs, a.a_roff = 0;
-      setw(ctx, a, L.item_qkv, L.item_qkv_h, pm.base);
+      L.item_qkv.gemm_operand(a, pm.base);
       a.M = TM * N, a.N = 3 * E, a.K = E;
       a.q = Qi, a.k = Ki, a.v = Vi, a.S = S, a.Npad = Npad, a.T = TM, a.H = H;
       HIPCHK(launch_gemm(a, pm.base, EPI_ITEM_QKV, true, true, 1, st));
       if (Q > 0) {
         GemmArgs c = a;
         c.a_rdiv = Q, c.a_roff = N;
-        setw(ctx, c, L.item_qtest, L.item_qtest_h, pm.base);
+        L.item_qtest.gemm_operand(c, pm.base);
         c.M = TM * Q, c.N = E;
         HIPCHK(launch_gemm(c, pm.base, EPI_ITEM_QKV, true, true, 1, st));
       }
@@ -721,23 +631,21 @@ int mlp_sublayer(mmpfn_ctx* ctx, const LayerW& L, void* Xv, int64_t RM, PrecMode
   const mmpfn_model_desc& d = ctx->d;
   float* Xall = (float*)Xv;
   if (pm.is16()) {
-    // bf16: W1 / W2 copies in mlp_rows_kernel's K orders; fp16: W1 natural, W2 / Wout rows in f16_row_perm order
-    const bool h16 = pm.f16();
-    const DevBuf& wout = h16 ? L.item_out_f : L.item_out_h;
-    HIPCHK(launch_mlp_rows(Xv, h16 ? L.mlp1_f.p : L.mlp1_h.p, h16 ? L.mlp2_f.p : L.mlp2_h.p, RM, d.emsize, d.nhid,
-                           d.ln_eps, ctx->stream, O, O ? wout.p : nullptr, pm.state()));
+    const DType t = pm.w16();
+    HIPCHK(launch_mlp_rows(Xv, L.mlp1.op16(t), L.mlp2.op16(t), RM, d.emsize, d.nhid, d.ln_eps, ctx->stream, O,
+                           O ? L.item_out.op16(t) : nullptr, pm.state()));
   } else if (pm.base == PREC_F32) {  // parity mode: mlp_x3_kernel on split-bf16 products (W1 / W2 hi | lo planes)
-    const auto w1 = ctx->split.find(L.mlp1.p), w2 = ctx->split.find(L.mlp2_h.p);  // W1 natural, W2 permuted
-    if (w1 == ctx->split.end() || w2 == ctx->split.end()) return fail(ctx, MMPFN_ERR_STATE, "no split MLP weights");
-    HIPCHK(launch_mlp_fused(Xall, w1->second.p, w2->second.p, RM, d.emsize, d.nhid, d.ln_eps, PREC_F32, ctx->stream));
+    HIPCHK(launch_mlp_fused(Xall, L.mlp1.split.p, L.mlp2.split.p, RM, d.emsize, d.nhid, d.ln_eps, PREC_F32,
+                            ctx->stream));
   } else {
-    HIPCHK(launch_mlp_fused(Xall, L.mlp1.p, L.mlp2.p, RM, d.emsize, d.nhid, d.ln_eps, PREC_F32_MFMA, ctx->stream));
+    HIPCHK(launch_mlp_fused(Xall, L.mlp1.f32.p, L.mlp2.f32.p, RM, d.emsize, d.nhid, d.ln_eps, PREC_F32_MFMA,
+                            ctx->stream));
   }
   return MMPFN_OK;
 }
 
 int run_layer(mmpfn_ctx* ctx, int l) {
-  const LayerW& L = ctx->layers[l];
+  const LayerW& L = ctx->w.layers[l];
   const int S = ctx->S, T = ctx->T, N = ctx->N, Npad = ctx->Npad, M = ctx->M;
   const PrecMode pm = lane_prec(*ctx);
   void* Xall = ctx->ws_X.p;
@@ -757,7 +665,7 @@ int run_layer(mmpfn_ctx* ctx, int l) {
 // Afterwards the state holds this layer's output at those rows only; every other row is left as this layer's
 // feature attention or the layer before wrote it.
 int last_layer_tail(mmpfn_ctx* ctx, int l) {
-  const LayerW& L = ctx->layers[l];
+  const LayerW& L = ctx->w.layers[l];
   const int S = ctx->S, T = ctx->T, N = ctx->N, Npad = ctx->Npad, M = ctx->M, E = ctx->d.emsize;
   const PrecMode pm = lane_prec(*ctx);
   const bool fuse = pm.is16();
@@ -783,14 +691,7 @@ int run_forward_layers(mmpfn_ctx* ctx) {
 }
 
 // workspace of the selected lane for a per-sublayer tap on a caller-provided state of S x T tokens
-int tap_workspace(mmpfn_ctx* ctx, int S, int T, int Npad) {
-  const int E = ctx->d.emsize;
-  const size_t R = (size_t)S * T;
-  const size_t Tpad = (T + 63) / 64 * 64;
-  RC(ensure(ctx, ctx->ws_O, R * E * 4));
-  RC(ensure(ctx, ctx->ws_big, std::max(R * E + 2 * S * Tpad * E, R * E + (size_t)2 * T * Npad * E) * 4));
-  return MMPFN_OK;
-}
+int tap_workspace(mmpfn_ctx* ctx, int S, int T, int Npad) { return lane_workspace(ctx, S, T, Npad, 1, false); }
 
 // decoder over the test rows of M batched members (logits [M][Q][n_out]); the tile partials go
 // through the attention-output workspace, free once the last layer has run
@@ -801,12 +702,12 @@ int decode(mmpfn_ctx* ctx, float* logits, int M = 1) {
   const size_t off = ((size_t)(T - 1) * S + N) * E;
   const float* Xl = (const float*)ctx->ws_X.p + off;
   int64_t xm = (int64_t)S * T * E;
-  if (pm.is16() && ctx->dec_w1_h.p) {  // the state as it is (fp32 / fp16) into 16-bit MFMA operands
-    const bool h = pm.f16();
+  const ModelWeights& w = ctx->w;
+  if (pm.is16() && w.dec_w1.bf16.p) {  // the state as it is (fp32 / fp16) into 16-bit MFMA operands
     const void* X = (const char*)ctx->ws_X.p + off * pm.state_bytes();
-    HIPCHK(launch_decoder_mfma(X, pm.state(), Q, h ? ctx->dec_w1_f.p : ctx->dec_w1_h.p, (const float*)ctx->dec_b1.p,
-                               d.nhid, h ? ctx->dec_w2p_f.p : ctx->dec_w2p_h.p, (const float*)ctx->dec_b2.p, d.n_out,
-                               logits, E, ctx->stream, M, xm, (int64_t)Q * d.n_out));
+    HIPCHK(launch_decoder_mfma(X, pm.state(), Q, w.dec_w1.op16(pm.w16()), (const float*)w.dec_b1.p, d.nhid,
+                               w.dec_w2.op16(pm.w16()), (const float*)w.dec_b2.p, d.n_out, logits, E, ctx->stream, M,
+                               xm, (int64_t)Q * d.n_out));
     return MMPFN_OK;
   }
   if (pm.f16()) {  // the target token's test rows of every member to fp32 (the big workspace is free)
@@ -816,8 +717,8 @@ int decode(mmpfn_ctx* ctx, float* logits, int M = 1) {
     Xl = (const float*)ctx->ws_big.p, xm = (int64_t)Q * E;
   }
   RC(ensure(ctx, ctx->ws_O, (size_t)M * (d.nhid / 32 + 1) * Q * d.n_out * sizeof(float)));
-  HIPCHK(launch_decoder(Xl, Q, (const float*)ctx->dec_w1.p, (const float*)ctx->dec_b1.p, d.nhid,
-                        (const float*)ctx->dec_w2.p, (const float*)ctx->dec_b2.p, d.n_out, logits, E, ctx->stream, M,
+  HIPCHK(launch_decoder(Xl, Q, (const float*)w.dec_w1.f32.p, (const float*)w.dec_b1.p, d.nhid,
+                        (const float*)w.dec_w2.f32.p, (const float*)w.dec_b2.p, d.n_out, logits, E, ctx->stream, M,
                         xm, (int64_t)Q * d.n_out, (float*)ctx->ws_O.p));
   return MMPFN_OK;
 }
@@ -828,7 +729,7 @@ int decode(mmpfn_ctx* ctx, float* logits, int M = 1) {
 // bank (mgm_f16_shape), else in the bf16 mode: fp16's 3 extra mantissa bits cut the mixer's share of the logits
 // error ~7x, and the reference's own fp16 autocast runs these linears in fp16.
 DType mgm_operands(const mmpfn_ctx* ctx, PrecMode pm) {
-  return !pm.is16() ? DType::F32 : pm.f16() && ctx->mgm_w1_f.p ? DType::F16 : DType::BF16;
+  return !pm.is16() ? DType::F32 : pm.f16() && ctx->w.mgm.w1.f16.p ? DType::F16 : DType::BF16;
 }
 
 int mixer_mgm(mmpfn_ctx* ctx, const float* image, int S, int n_mod, void* mtok, PrecMode pm,
@@ -836,7 +737,8 @@ int mixer_mgm(mmpfn_ctx* ctx, const float* image, int S, int n_mod, void* mtok, 
   const mmpfn_model_desc& d = ctx->d;
   const int E = d.emsize, D = d.nhid;
   const DType t = mgm_operands(ctx, pm);
-  const bool b16 = pm.is16(), h = t == DType::F16;
+  const HeadBank& w = ctx->w.mgm;
+  const bool b16 = pm.is16();
   const int eb = pm.op_bytes();
   hipStream_t st = ctx->stream;
   const int64_t rows = (int64_t)S * n_mod;
@@ -845,24 +747,24 @@ int mixer_mgm(mmpfn_ctx* ctx, const float* image, int S, int n_mod, void* mtok, 
   RC(ensure(ctx, ctx->mx[1], (size_t)rows * mg * (D / 2) * eb));  // GLU output
   HIPCHK(launch_layernorm_rows(image, rows, D, 1e-5f, ctx->mx[0].p, t, nullptr, nullptr, st));
   if (b16 && (mg * D) % 256 == 0) {
-    HIPCHK(launch_gemm_glu_big(ctx->mx[0].p, h ? ctx->mgm_w1_f.p : ctx->mgm_w1_h.p, (const float*)ctx->mgm_b1.p,
+    HIPCHK(launch_gemm_glu_big(ctx->mx[0].p, w.w1.op16(t), (const float*)w.b1.p,
                                ctx->mx[1].p, (int)rows, mg * D, D, st, t));
   } else {
     GemmArgs a = gargs();
-    a.A = ctx->mx[0].p, a.lda = D, setw(ctx, a, ctx->mgm_w1, ctx->mgm_w1_h, pm.gemm());
-    a.bias = (const float*)ctx->mgm_b1.p;
+    a.A = ctx->mx[0].p, a.lda = D, w.w1.gemm_operand(a, pm.gemm());
+    a.bias = (const float*)w.b1.p;
     a.M = (int)rows, a.N = mg * D, a.K = D, a.C = ctx->mx[1].p, a.ldc = (int64_t)mg * (D / 2);
     HIPCHK(launch_gemm(a, pm.gemm(), EPI_GLU, !b16, !b16, 1, st));
   }
   if (b16) {  // the big-tile down-projection (16-bit tokens possible)
-    HIPCHK(launch_gemm_remap_big(ctx->mx[1].p, (int64_t)mg * (D / 2), h ? ctx->mgm_w2_f.p : ctx->mgm_w2_h.p,
-                                 (const float*)ctx->mgm_b2.p, mtok, tok_t, (int)rows, D / 2, mg, n_mod, E, st, t));
+    HIPCHK(launch_gemm_remap_big(ctx->mx[1].p, (int64_t)mg * (D / 2), w.w2.op16(t),
+                                 (const float*)w.b2.p, mtok, tok_t, (int)rows, D / 2, mg, n_mod, E, st, t));
     return MMPFN_OK;
   }
   GemmArgs b = gargs();
   b.A = ctx->mx[1].p, b.lda = (int64_t)mg * (D / 2), b.a_zstride = D / 2;
-  setw(ctx, b, ctx->mgm_w2, ctx->mgm_w2_h, pm.base), b.w_zstride = (int64_t)E * (D / 2);
-  b.bias = (const float*)ctx->mgm_b2.p, b.b_zstride = E;
+  w.w2.gemm_operand(b, pm.base), b.w_zstride = (int64_t)E * (D / 2);
+  b.bias = (const float*)w.b2.p, b.b_zstride = E;
   b.M = (int)rows, b.N = E, b.K = D / 2;
   b.C = mtok, b.ldc = E, b.rdiv2 = n_mod, b.rmul2 = M, b.zmul = n_mod;
   HIPCHK(launch_gemm(b, pm.base, EPI_REMAP, true, true, mg, st));
@@ -878,6 +780,7 @@ int mixer_cap(mmpfn_ctx* ctx, const void* mtok, int S, int M, float* tokens, Pre
   const int eb = pm.op_bytes();
   hipStream_t st = ctx->stream;
   const int cap = d.cap_heads;
+  const ModelWeights& w = ctx->w;
   const int64_t srows = (int64_t)S * M;
   RC(ensure(ctx, ctx->mx[3], (size_t)srows * E * eb));        // k_norm(src) (affine folded)
   RC(ensure(ctx, ctx->mx[4], (size_t)srows * 2 * E * eb));    // K|V
@@ -890,43 +793,37 @@ int mixer_cap(mmpfn_ctx* ctx, const void* mtok, int S, int M, float* tokens, Pre
     const bool mf = cap == 24 && M % 32 == 0 && M <= 128;
     void* vt = (char*)ctx->mx[4].p + (size_t)srows * E * 2;
     // k_norm + K|V projection in one row pass (normalised rows stay in registers)
-    HIPCHK(launch_rowgemm_ln_store(mtok, in_t, ctx->cap_kv_h.p, (const float*)ctx->cap_kv_b.p, ctx->mx[4].p, srows,
+    HIPCHK(launch_rowgemm_ln_store(mtok, in_t, w.cap_kv.bf16.p, (const float*)w.cap_kv_b.p, ctx->mx[4].p, srows,
                                    2 * E, 1e-5f, true, st, mf ? vt : nullptr, E, M));
     // attention out in bf16, then the whole tail in one row-resident pass
     if (mf)
-      HIPCHK(launch_cap_attention_mfma((const float*)ctx->cap_qp.p, ctx->mx[4].p, vt, ctx->mx[5].p, S, M, cap, E, st));
+      HIPCHK(launch_cap_attention_mfma((const float*)w.cap_qp.p, ctx->mx[4].p, vt, ctx->mx[5].p, S, M, cap, E, st));
     else
-      HIPCHK(launch_cap_attention((const float*)ctx->cap_qp.p, ctx->mx[4].p, DType::BF16, ctx->mx[5].p, DType::BF16, S,
+      HIPCHK(launch_cap_attention((const float*)w.cap_qp.p, ctx->mx[4].p, DType::BF16, ctx->mx[5].p, DType::BF16, S,
                                   M, cap, E, st));
-    HIPCHK(launch_cap_tail(ctx->mx[5].p, ctx->cap_o_h.p, ctx->cap_f0_p.p, ctx->cap_f3_p.p,
-                           (const float*)ctx->cap_vecs.p, tokens, crow, E, 1e-5f, st));
+    HIPCHK(launch_cap_tail(ctx->mx[5].p, w.cap_o.bf16.p, w.cap_f0.bf16.p, w.cap_f3.bf16.p, (const float*)w.cap_vecs.p,
+                           tokens, crow, E, 1e-5f, st));
     return MMPFN_OK;
   }
   // the fp32 modes: fp32 activations throughout
   const int prec = pm.base;
   HIPCHK(launch_layernorm_rows((const float*)mtok, srows, E, 1e-5f, ctx->mx[3].p, DType::F32, nullptr, nullptr, st));
-  GemmArgs c = gargs();
-  c.A = ctx->mx[3].p, c.lda = E, setw(ctx, c, ctx->cap_kv, ctx->cap_kv_h, prec), c.bias = (const float*)ctx->cap_kv_b.p;
-  c.M = (int)srows, c.N = 2 * E, c.K = E, c.C = ctx->mx[4].p, c.ldc = 2 * E;
-  HIPCHK(launch_gemm(c, prec, EPI_STORE, true, true, 1, st));
-  HIPCHK(launch_cap_attention((const float*)ctx->cap_qp.p, ctx->mx[4].p, DType::F32, ctx->mx[5].p, DType::F32, S, M, cap,
+  // C [rows][N] = act(A [rows][K] . W^T + bias)
+  auto linear = [&](const DevBuf& A, const Weight& W, const DevBuf& bias, int64_t rows, int N, int K, int act,
+                    const DevBuf& C) {
+    GemmArgs g = gargs();
+    g.A = A.p, g.lda = K, W.gemm_operand(g, prec), g.bias = (const float*)bias.p, g.act = act;
+    g.M = (int)rows, g.N = N, g.K = K, g.C = C.p, g.ldc = N;
+    return launch_gemm(g, prec, EPI_STORE, true, true, 1, st);
+  };
+  HIPCHK(linear(ctx->mx[3], w.cap_kv, w.cap_kv_b, srows, 2 * E, E, ACT_NONE, ctx->mx[4]));
+  HIPCHK(launch_cap_attention((const float*)w.cap_qp.p, ctx->mx[4].p, DType::F32, ctx->mx[5].p, DType::F32, S, M, cap,
                               E, st));
-  GemmArgs o = gargs();
-  o.A = ctx->mx[5].p, o.lda = E, setw(ctx, o, ctx->cap_o, ctx->cap_o_h, prec), o.bias = (const float*)ctx->cap_o_b.p;
-  o.M = (int)crow, o.N = E, o.K = E, o.C = ctx->mx[6].p, o.ldc = E;
-  HIPCHK(launch_gemm(o, prec, EPI_STORE, true, true, 1, st));
-  GemmArgs f0 = gargs();
-  f0.A = ctx->mx[6].p, f0.lda = E, setw(ctx, f0, ctx->cap_f0, ctx->cap_f0_h, prec);
-  f0.bias = (const float*)ctx->cap_f0_b.p, f0.act = ACT_GELU;
-  f0.M = (int)crow, f0.N = 2 * E, f0.K = E, f0.C = ctx->mx[7].p, f0.ldc = 2 * E;
-  HIPCHK(launch_gemm(f0, prec, EPI_STORE, true, true, 1, st));
-  GemmArgs f3 = gargs();
-  f3.A = ctx->mx[7].p, f3.lda = 2 * E, setw(ctx, f3, ctx->cap_f3, ctx->cap_f3_h, prec);
-  f3.bias = (const float*)ctx->cap_f3_b.p;
-  f3.M = (int)crow, f3.N = E, f3.K = 2 * E, f3.C = ctx->mx[5].p, f3.ldc = E;  // reuse mx5 for ffn out
-  HIPCHK(launch_gemm(f3, prec, EPI_STORE, true, true, 1, st));
-  HIPCHK(launch_ln_add((const float*)ctx->mx[6].p, (const float*)ctx->mx[5].p, (const float*)ctx->cap_ng.p,
-                       (const float*)ctx->cap_nb.p, tokens, crow, E, 1e-5f, st));
+  HIPCHK(linear(ctx->mx[5], w.cap_o, w.cap_o_b, crow, E, E, ACT_NONE, ctx->mx[6]));
+  HIPCHK(linear(ctx->mx[6], w.cap_f0, w.cap_f0_b, crow, 2 * E, E, ACT_GELU, ctx->mx[7]));
+  HIPCHK(linear(ctx->mx[7], w.cap_f3, w.cap_f3_b, crow, E, 2 * E, ACT_NONE, ctx->mx[5]));  // reuse mx5 for ffn out
+  HIPCHK(launch_ln_add((const float*)ctx->mx[6].p, (const float*)ctx->mx[5].p, (const float*)w.cap_ng.p,
+                       (const float*)w.cap_nb.p, tokens, crow, E, 1e-5f, st));
   return MMPFN_OK;
 }
 
@@ -947,6 +844,7 @@ int mixer(mmpfn_ctx* ctx, const float* image, int S, int n_mod, float* tokens, P
   hipStream_t st = ctx->stream;
   if (d.mixer_type == MMPFN_MIXER_MOE) {
     const int ne = d.mgm_heads;
+    const HeadBank& w = ctx->w.moe;
     RC(ensure(ctx, ctx->mx[0], (size_t)S * D * eb));
     RC(ensure(ctx, ctx->mx[1], (size_t)S * ne * (D / 2) * eb));
     RC(ensure(ctx, ctx->mx[2], (size_t)S * ne * 4));
@@ -962,16 +860,16 @@ int mixer(mmpfn_ctx* ctx, const float* image, int S, int n_mod, float* tokens, P
     }
     HIPCHK(launch_layernorm_rows(x0, S, D, 1e-5f, ctx->mx[0].p, b16 ? DType::BF16 : DType::F32, nullptr, nullptr, st));
     GemmArgs a = gargs();
-    a.A = ctx->mx[0].p, a.lda = D, setw(ctx, a, ctx->moe_w1, ctx->moe_w1_h, prec), a.bias = (const float*)ctx->moe_b1.p;
+    a.A = ctx->mx[0].p, a.lda = D, w.w1.gemm_operand(a, prec), a.bias = (const float*)w.b1.p;
     a.act = ACT_GELU, a.M = S, a.N = ne * (D / 2), a.K = D, a.C = ctx->mx[1].p, a.ldc = (int64_t)ne * (D / 2);
     HIPCHK(launch_gemm(a, prec, EPI_STORE, !b16, !b16, 1, st));
     GemmArgs b = gargs();
     b.A = ctx->mx[1].p, b.lda = (int64_t)ne * (D / 2), b.a_zstride = D / 2;
-    setw(ctx, b, ctx->moe_w2, ctx->moe_w2_h, prec), b.w_zstride = (int64_t)E * (D / 2);
-    b.bias = (const float*)ctx->moe_b2.p, b.b_zstride = E;
+    w.w2.gemm_operand(b, prec), b.w_zstride = (int64_t)E * (D / 2);
+    b.bias = (const float*)w.b2.p, b.b_zstride = E;
     b.M = S, b.N = E, b.K = D / 2, b.C = tokens, b.ldc = E, b.rdiv2 = 1, b.rmul2 = ne, b.zmul = 1;
     HIPCHK(launch_gemm(b, prec, EPI_REMAP, !b16, true, ne, st));
-    HIPCHK(launch_gate_softmax(x0, D, S, D, (const float*)ctx->moe_gw.p, (const float*)ctx->moe_gb.p, ne,
+    HIPCHK(launch_gate_softmax(x0, D, S, D, (const float*)ctx->w.moe_gw.p, (const float*)ctx->w.moe_gb.p, ne,
                                (float*)ctx->mx[2].p, st));
     HIPCHK(launch_scale_tokens(tokens, (const float*)ctx->mx[2].p, S, ne, E, st));
     return MMPFN_OK;
@@ -1072,6 +970,7 @@ int mmpfn_finalize_weights(mmpfn_ctx* ctx) {
   if (!ctx) return MMPFN_ERR_INVALID;
   if (!ctx->have_model) return fail(ctx, MMPFN_ERR_STATE, "mmpfn_set_model first");
   HIPCHK(hipSetDevice(ctx->device));
+  ctx->finalized = false;  // finalize releases the previous weights before anything can fail
   int rc = finalize(ctx);
   if (rc == MMPFN_OK) {
     ctx->finalized = true;
@@ -1109,7 +1008,7 @@ int mmpfn_embed(mmpfn_ctx* ctx, const float* x, int S, int F, const float* token
 
 int mmpfn_run_layers(mmpfn_ctx* ctx, int l0, int l1) {
   if (!ctx) return MMPFN_ERR_INVALID;
-  if (!ctx->embedded) return fail(ctx, MMPFN_ERR_STATE, "mmpfn_embed first");
+  if (!ctx->embedded || !ctx->finalized) return fail(ctx, MMPFN_ERR_STATE, "mmpfn_embed first");
   if (l0 < 0 || l1 > ctx->d.nlayers || l0 > l1) return fail(ctx, MMPFN_ERR_INVALID, "bad layer range");
   HIPCHK(hipSetDevice(ctx->device));
   for (int l = l0; l < l1; ++l) RC(run_layer(ctx, l));
@@ -1118,7 +1017,7 @@ int mmpfn_run_layers(mmpfn_ctx* ctx, int l0, int l1) {
 
 int mmpfn_decode(mmpfn_ctx* ctx, float* logits) {
   if (!ctx || !logits) return MMPFN_ERR_INVALID;
-  if (!ctx->embedded) return fail(ctx, MMPFN_ERR_STATE, "mmpfn_embed first");
+  if (!ctx->embedded || !ctx->finalized) return fail(ctx, MMPFN_ERR_STATE, "mmpfn_embed first");
   HIPCHK(hipSetDevice(ctx->device));
   return decode(ctx, logits);
 }
@@ -1369,7 +1268,7 @@ int mmpfn_feature_attention(mmpfn_ctx* ctx, int layer, float* X, int S, int T, i
   RC(tap_workspace(ctx, S, T, 64));
   const PrecMode pm = decode_prec(precision, T);
   return state_tap(ctx, X, (int64_t)S * T * ctx->d.emsize, pm, [&](void* Xs) {
-    return feat_sublayer(ctx, ctx->layers[layer], Xs, S, T, 1, pm);
+    return feat_sublayer(ctx, ctx->w.layers[layer], Xs, S, T, 1, pm);
   });
 }
 
@@ -1389,7 +1288,7 @@ int mmpfn_mlp_ln(mmpfn_ctx* ctx, int layer, float* X, int64_t rows, int precisio
   if (rows <= 0) return fail(ctx, MMPFN_ERR_INVALID, "bad row count");
   const PrecMode pm = decode_prec(precision, -1);  // row-wise: no token limit
   return state_tap(ctx, X, rows * ctx->d.emsize, pm, [&](void* Xs) {
-    return mlp_sublayer(ctx, ctx->layers[layer], Xs, rows, pm, nullptr);
+    return mlp_sublayer(ctx, ctx->w.layers[layer], Xs, rows, pm, nullptr);
   });
 }
 

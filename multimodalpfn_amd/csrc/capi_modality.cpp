@@ -34,7 +34,8 @@ namespace {
 struct EncLayer {
   // ViT: ln1 = norm1, ln2 = norm2 (pre-LN); text: ln1 = attention.output.LayerNorm, ln2 = output.LayerNorm
   DevBuf ln1g, ln1b, ln2g, ln2b, ls1, ls2;
-  DevBuf qkv, qkv_h, qkv_b, proj, proj_h, proj_b, fc1, fc1_h, fc1_b, fc2, fc2_h, fc2_b;
+  Weight qkv, proj, fc1, fc2;  // fp32 and bf16, both natural [N][K]
+  DevBuf qkv_b, proj_b, fc1_b, fc2_b;
 };
 
 }  // namespace
@@ -48,9 +49,10 @@ struct mmpfn_enc {
   std::map<std::string, std::vector<float>> host;
   std::vector<EncLayer> layers;
   int Kpad = 0;  // ViT patch GEMM K (C * P * P rounded up to 64)
-  DevBuf pe_w, pe_wh, pe_b, cls_tok, pos, norm_g, norm_b;
+  Weight pe_w, eproj;  // (as EncLayer's)
+  DevBuf pe_b, cls_tok, pos, norm_g, norm_b;
   std::map<std::pair<int, int>, DevBuf> pos_cache;  // interpolated pos_embed per (grid h, grid w)
-  DevBuf wemb, pemb, temb, emb_g, emb_b, eproj, eproj_h, eproj_b;
+  DevBuf wemb, pemb, temb, emb_g, emb_b, eproj_b;
   // workspace
   DevBuf X, A, QKV, O, Hh, Y, Xc, Ac, Oc, Hc, Yc, kb, flag, P0;
 };
@@ -61,11 +63,9 @@ namespace {
 #define GETW(var, name, n) GETW_ON(enc, var, name, n)
 
 // a Linear's weight in both dtypes (fp32 for the parity mode, bf16 for the MFMA path) + bias
-int up_linear(mmpfn_enc* enc, DevBuf& w, DevBuf& wh, DevBuf& b, const std::vector<float>& wv, const std::vector<float>& bv) {
-  RC(upload(enc, w, wv));
-  RC(upload(enc, wh, wv, DType::BF16));
-  RC(upload(enc, b, bv));
-  return MMPFN_OK;
+int up_linear(mmpfn_enc* enc, Weight& w, DevBuf& b, const std::vector<float>& wv, const std::vector<float>& bv) {
+  RC(fill(enc, w, wv, Weight::F32 | Weight::BF16));
+  return upload(enc, b, bv);
 }
 
 int finalize_vit(mmpfn_enc* enc) {
@@ -79,7 +79,7 @@ int finalize_vit(mmpfn_enc* enc) {
     std::vector<float> wp((size_t)D * enc->Kpad, 0.f);
     for (int n = 0; n < D; ++n)
       for (int k = 0; k < K0; ++k) wp[(size_t)n * enc->Kpad + k] = (*w)[(size_t)n * K0 + k];
-    RC(up_linear(enc, enc->pe_w, enc->pe_wh, enc->pe_b, wp, *b));
+    RC(up_linear(enc, enc->pe_w, enc->pe_b, wp, *b));
   }
   {
     GETW(c, "cls_token", (size_t)D);
@@ -112,10 +112,10 @@ int finalize_vit(mmpfn_enc* enc) {
     RC(upload(enc, L.ln1b, *n1b));
     RC(upload(enc, L.ln2g, *n2g));
     RC(upload(enc, L.ln2b, *n2b));
-    RC(up_linear(enc, L.qkv, L.qkv_h, L.qkv_b, *qw, *qb));
-    RC(up_linear(enc, L.proj, L.proj_h, L.proj_b, *pw, *pb));
-    RC(up_linear(enc, L.fc1, L.fc1_h, L.fc1_b, *f1w, *f1b));
-    RC(up_linear(enc, L.fc2, L.fc2_h, L.fc2_b, *f2w, *f2b));
+    RC(up_linear(enc, L.qkv, L.qkv_b, *qw, *qb));
+    RC(up_linear(enc, L.proj, L.proj_b, *pw, *pb));
+    RC(up_linear(enc, L.fc1, L.fc1_b, *f1w, *f1b));
+    RC(up_linear(enc, L.fc2, L.fc2_b, *f2w, *f2b));
     if (d.layerscale) {
       GETW(g1, pre + "ls1.gamma", D);
       GETW(g2, pre + "ls2.gamma", D);
@@ -143,7 +143,7 @@ int finalize_text(mmpfn_enc* enc) {
     if (E != D) {
       GETW(pw, "embeddings_project.weight", (size_t)D * E);
       GETW(pb, "embeddings_project.bias", D);
-      RC(up_linear(enc, enc->eproj, enc->eproj_h, enc->eproj_b, *pw, *pb));
+      RC(up_linear(enc, enc->eproj, enc->eproj_b, *pw, *pb));
     }
   }
   enc->layers.clear();
@@ -172,10 +172,10 @@ int finalize_text(mmpfn_enc* enc) {
     w3.insert(w3.end(), vw->begin(), vw->end());
     b3.insert(b3.end(), kb->begin(), kb->end());
     b3.insert(b3.end(), vb->begin(), vb->end());
-    RC(up_linear(enc, L.qkv, L.qkv_h, L.qkv_b, w3, b3));
-    RC(up_linear(enc, L.proj, L.proj_h, L.proj_b, *ow, *ob));
-    RC(up_linear(enc, L.fc1, L.fc1_h, L.fc1_b, *iw, *ib));
-    RC(up_linear(enc, L.fc2, L.fc2_h, L.fc2_b, *o2w, *o2b));
+    RC(up_linear(enc, L.qkv, L.qkv_b, w3, b3));
+    RC(up_linear(enc, L.proj, L.proj_b, *ow, *ob));
+    RC(up_linear(enc, L.fc1, L.fc1_b, *iw, *ib));
+    RC(up_linear(enc, L.fc2, L.fc2_b, *o2w, *o2b));
     RC(upload(enc, L.ln1g, *l1g));
     RC(upload(enc, L.ln1b, *l1b));
     RC(upload(enc, L.ln2g, *l2g));
@@ -184,22 +184,20 @@ int finalize_text(mmpfn_enc* enc) {
   return MMPFN_OK;
 }
 
-inline const void* Wsel(const DevBuf& f, const DevBuf& h, int prec) { return prec == PREC_BF16 ? h.p : f.p; }
-
 // C = A . W^T + bias, epilogue per mode; fp32 parity mode: the generic fp32-MFMA GEMM (gemm.hip)
 // into Y, then the residual / store step
-int linear(mmpfn_enc* enc, int prec, const void* A, const DevBuf& Wf, const DevBuf& Wh, const DevBuf& bias, int M, int N,
-           int K, int epi, int act, void* C, const float* gamma, float* Y) {
+int linear(mmpfn_enc* enc, int prec, const void* A, const Weight& W, const DevBuf& bias, int M, int N, int K, int epi,
+           int act, void* C, const float* gamma, float* Y) {
   if (M <= 0) return MMPFN_OK;
   if (prec == PREC_BF16) {
-    HIPCHK(launch_gemm_tile(A, Wh.p, (const float*)bias.p, gamma, C, N, M, N, K, epi, act, enc->stream));
+    HIPCHK(launch_gemm_tile(A, W.bf16.p, (const float*)bias.p, gamma, C, N, M, N, K, epi, act, enc->stream));
     return MMPFN_OK;
   }
   if (N % 192 != 0) return fail(enc, MMPFN_ERR_INVALID, "fp32 mode needs linear widths that are multiples of 192");
   GemmArgs g;
   std::memset(&g, 0, sizeof(g));
   g.a_rdiv = 1ll << 62, g.a_rmul = 0, g.a_rmul2 = 1, g.rdiv2 = 1ll << 62, g.ln_eps = 1e-5f;
-  g.A = A, g.lda = K, g.W = Wf.p, g.bias = (const float*)bias.p, g.M = M, g.N = N, g.K = K, g.act = act;
+  g.A = A, g.lda = K, g.W = W.f32.p, g.bias = (const float*)bias.p, g.M = M, g.N = N, g.K = K, g.act = act;
   g.C = epi == GT_RESID ? (void*)Y : C, g.ldc = N;
   // the encoders' fp32 mode stays on fp32-input MFMA (their 1-2e-6 parity; the tower runs once per dataset)
   HIPCHK(launch_gemm(g, PREC_F32_MFMA, EPI_STORE, true, true, 1, enc->stream));
@@ -264,7 +262,7 @@ int cls_tail(mmpfn_enc* enc, const EncLayer& Lw, int B, int64_t L, int prec, boo
   hipStream_t st = enc->stream;
   HIPCHK(launch_gather_rows(enc->X.p, L * D, B, D, enc->Xc.p, 4, st));
   float* Xc = (float*)enc->Xc.p;
-  RC(linear(enc, prec, enc->Oc.p, Lw.proj, Lw.proj_h, Lw.proj_b, B, D, D, GT_RESID, 0, Xc,
+  RC(linear(enc, prec, enc->Oc.p, Lw.proj, Lw.proj_b, B, D, D, GT_RESID, 0, Xc,
             post_ln ? nullptr : (const float*)Lw.ls1.p, (float*)enc->Yc.p));
   const bool bf = prec == PREC_BF16;
   if (post_ln) {
@@ -275,8 +273,8 @@ int cls_tail(mmpfn_enc* enc, const EncLayer& Lw, int B, int64_t L, int prec, boo
                           (const float*)Lw.ln2g.p, (const float*)Lw.ln2b.p, st));
   }
   const void* Ain = post_ln && !bf ? (const void*)Xc : enc->Ac.p;
-  RC(linear(enc, prec, Ain, Lw.fc1, Lw.fc1_h, Lw.fc1_b, B, F, D, GT_BF16, 1, enc->Hc.p, nullptr, nullptr));
-  RC(linear(enc, prec, enc->Hc.p, Lw.fc2, Lw.fc2_h, Lw.fc2_b, B, D, F, GT_RESID, 0, Xc,
+  RC(linear(enc, prec, Ain, Lw.fc1, Lw.fc1_b, B, F, D, GT_BF16, 1, enc->Hc.p, nullptr, nullptr));
+  RC(linear(enc, prec, enc->Hc.p, Lw.fc2, Lw.fc2_b, B, D, F, GT_RESID, 0, Xc,
             post_ln ? nullptr : (const float*)Lw.ls2.p, (float*)enc->Yc.p));
   if (post_ln)
     HIPCHK(launch_ln_dual(Xc, B, D, eps, Xc, nullptr, (const float*)Lw.ln2g.p, (const float*)Lw.ln2b.p, st));
@@ -377,8 +375,7 @@ int mmpfn_vit_forward(mmpfn_enc* enc, const float* images, int B, int H, int W, 
   RC(pos_for(enc, gh, gw, &pe));
   // patch embedding: im2col + GEMM (+ bias) -> [cls | patches] + pos
   HIPCHK(launch_im2col(images, B, d.in_chans, H, W, P, enc->Kpad, enc->A.p, !bf, st));
-  RC(linear(enc, prec, enc->A.p, enc->pe_w, enc->pe_wh, enc->pe_b, B * np, D, enc->Kpad, GT_F32, 0, enc->P0.p,
-            nullptr, nullptr));
+  RC(linear(enc, prec, enc->A.p, enc->pe_w, enc->pe_b, B * np, D, enc->Kpad, GT_F32, 0, enc->P0.p, nullptr, nullptr));
   float* X = (float*)enc->X.p;
   HIPCHK(launch_vit_assemble((const float*)enc->P0.p, (const float*)enc->cls_tok.p, pe, B, np, D, X, st));
   for (int i = 0; i < d.depth; ++i) {
@@ -387,21 +384,20 @@ int mmpfn_vit_forward(mmpfn_enc* enc, const float* images, int B, int H, int W, 
     // X += ls1 * attn(norm1(X))   (block.py:106-115)
     HIPCHK(launch_ln_dual(X, M, D, eps, bf ? nullptr : (float*)enc->A.p, bf ? enc->A.p : nullptr,
                           (const float*)Lw.ln1g.p, (const float*)Lw.ln1b.p, st));
-    RC(linear(enc, prec, enc->A.p, Lw.qkv, Lw.qkv_h, Lw.qkv_b, (int)M, 3 * D, D, GT_BF16, 0, enc->QKV.p, nullptr,
-              nullptr));
+    RC(linear(enc, prec, enc->A.p, Lw.qkv, Lw.qkv_b, (int)M, 3 * D, D, GT_BF16, 0, enc->QKV.p, nullptr, nullptr));
     if (tail) {
       HIPCHK(launch_attn64(enc->QKV.p, nullptr, enc->Oc.p, B, (int)L, nh, 0, 1, 1, prec, st));
       RC(cls_tail(enc, Lw, B, L, prec, false));
       break;
     }
     HIPCHK(launch_attn64(enc->QKV.p, nullptr, enc->O.p, B, (int)L, nh, 0, (int)L, L, prec, st));
-    RC(linear(enc, prec, enc->O.p, Lw.proj, Lw.proj_h, Lw.proj_b, (int)M, D, D, GT_RESID, 0, X,
+    RC(linear(enc, prec, enc->O.p, Lw.proj, Lw.proj_b, (int)M, D, D, GT_RESID, 0, X,
               (const float*)Lw.ls1.p, (float*)enc->Y.p));
     // X += ls2 * mlp(norm2(X))
     HIPCHK(launch_ln_dual(X, M, D, eps, bf ? nullptr : (float*)enc->A.p, bf ? enc->A.p : nullptr,
                           (const float*)Lw.ln2g.p, (const float*)Lw.ln2b.p, st));
-    RC(linear(enc, prec, enc->A.p, Lw.fc1, Lw.fc1_h, Lw.fc1_b, (int)M, F, D, GT_BF16, 1, enc->Hh.p, nullptr, nullptr));
-    RC(linear(enc, prec, enc->Hh.p, Lw.fc2, Lw.fc2_h, Lw.fc2_b, (int)M, D, F, GT_RESID, 0, X,
+    RC(linear(enc, prec, enc->A.p, Lw.fc1, Lw.fc1_b, (int)M, F, D, GT_BF16, 1, enc->Hh.p, nullptr, nullptr));
+    RC(linear(enc, prec, enc->Hh.p, Lw.fc2, Lw.fc2_b, (int)M, D, F, GT_RESID, 0, X,
               (const float*)Lw.ls2.p, (float*)enc->Y.p));
   }
   // x_norm = norm(x); x_norm_clstoken = x_norm[:, 0]
@@ -462,12 +458,11 @@ int mmpfn_text_forward(mmpfn_enc* enc, const int32_t* ids, const int32_t* mask, 
                              (const float*)enc->temb.p, (const float*)enc->emb_g.p, (const float*)enc->emb_b.p,
                              eps, e32, bf ? e16 : nullptr, d.vocab, d.type_vocab, (int*)enc->flag.p, st));
     if (bf) {
-      HIPCHK(launch_gemm_tile(e16, enc->eproj_h.p, (const float*)enc->eproj_b.p, nullptr, X, D, (int)M, D, E,
+      HIPCHK(launch_gemm_tile(e16, enc->eproj.bf16.p, (const float*)enc->eproj_b.p, nullptr, X, D, (int)M, D, E,
                               GT_F32, 0, st));
       HIPCHK(launch_cast_bf16(X, enc->A.p, M * D, st));
     } else {
-      RC(linear(enc, prec, e32, enc->eproj, enc->eproj_h, enc->eproj_b, (int)M, D, E, GT_F32, 0, X, nullptr,
-                nullptr));
+      RC(linear(enc, prec, e32, enc->eproj, enc->eproj_b, (int)M, D, E, GT_F32, 0, X, nullptr, nullptr));
     }
   }
   for (int i = 0; i < d.depth; ++i) {
@@ -475,20 +470,18 @@ int mmpfn_text_forward(mmpfn_enc* enc, const int32_t* ids, const int32_t* mask, 
     const bool tail = i == d.depth - 1 && hidden == nullptr;
     // X = LN1(X + dense(attn(qkv(X))))   (ElectraSelfAttention / ElectraSelfOutput)
     const void* Ain = bf ? enc->A.p : (const void*)X;
-    RC(linear(enc, prec, Ain, Lw.qkv, Lw.qkv_h, Lw.qkv_b, (int)M, 3 * D, D, GT_BF16, 0, enc->QKV.p, nullptr, nullptr));
+    RC(linear(enc, prec, Ain, Lw.qkv, Lw.qkv_b, (int)M, 3 * D, D, GT_BF16, 0, enc->QKV.p, nullptr, nullptr));
     if (tail) {
       HIPCHK(launch_attn64(enc->QKV.p, kbias, enc->Oc.p, B, L, nh, 0, 1, 1, prec, st));
       RC(cls_tail(enc, Lw, B, L, prec, true));
       break;
     }
     HIPCHK(launch_attn64(enc->QKV.p, kbias, enc->O.p, B, L, nh, 0, L, L, prec, st));
-    RC(linear(enc, prec, enc->O.p, Lw.proj, Lw.proj_h, Lw.proj_b, (int)M, D, D, GT_RESID, 0, X, nullptr,
-              (float*)enc->Y.p));
+    RC(linear(enc, prec, enc->O.p, Lw.proj, Lw.proj_b, (int)M, D, D, GT_RESID, 0, X, nullptr, (float*)enc->Y.p));
     HIPCHK(launch_ln_dual(X, M, D, eps, X, bf ? enc->A.p : nullptr, (const float*)Lw.ln1g.p, (const float*)Lw.ln1b.p, st));
     // X = LN2(X + out(GELU(inter(X))))   (ElectraIntermediate / ElectraOutput)
-    RC(linear(enc, prec, Ain, Lw.fc1, Lw.fc1_h, Lw.fc1_b, (int)M, F, D, GT_BF16, 1, enc->Hh.p, nullptr, nullptr));
-    RC(linear(enc, prec, enc->Hh.p, Lw.fc2, Lw.fc2_h, Lw.fc2_b, (int)M, D, F, GT_RESID, 0, X, nullptr,
-              (float*)enc->Y.p));
+    RC(linear(enc, prec, Ain, Lw.fc1, Lw.fc1_b, (int)M, F, D, GT_BF16, 1, enc->Hh.p, nullptr, nullptr));
+    RC(linear(enc, prec, enc->Hh.p, Lw.fc2, Lw.fc2_b, (int)M, D, F, GT_RESID, 0, X, nullptr, (float*)enc->Y.p));
     HIPCHK(launch_ln_dual(X, M, D, eps, X, bf ? enc->A.p : nullptr, (const float*)Lw.ln2g.p, (const float*)Lw.ln2b.p, st));
   }
   if (hidden) {

@@ -136,7 +136,7 @@ hipError_t launch_rowgemm_resln(const void* O, const void* W, int64_t M, void* X
                                 DType x_t = DType::F32);
 
 // parity-mode (x3 split-bf16) row-resident projections of width 192 (rowgemm3.hip), fp32 in and out:
-// W = the hi plane [N][192] of capi.cpp upsplit, its lo plane at W + w_lo elements.
+// W = the hi plane [N][192] of split_bf16 (weight_pack.h), its lo plane at W + w_lo elements.
 //   QKV: up to two row sets in one launch (same remap / scatter as launch_rowgemm_qkv, fp32 Q / K / V^T)
 //   RES_LN: X <- LN(X + O . W^T), O fp32 [M][192]
 struct Proj3Set {

@@ -46,6 +46,70 @@ inline uint16_t f2h(float f) {
   return (uint16_t)(sign | r);
 }
 
+// the parity mode's weight operand: v as bf16 planes [hi | lo], hi = bf16(v), lo = bf16(v - hi)
+inline std::vector<uint16_t> split_bf16(const std::vector<float>& v) {
+  std::vector<uint16_t> h(2 * v.size());
+  for (size_t i = 0; i < v.size(); ++i) {
+    const uint16_t hi = f2bf(v[i]);
+    uint32_t u = (uint32_t)hi << 16;
+    float fh;
+    std::memcpy(&fh, &u, 4);
+    h[i] = hi;
+    h[v.size() + i] = f2bf(v[i] - fh);
+  }
+  return h;
+}
+
+// the first nq elements of w (the Q rows of an item-attention projection) times the attention kernel's
+// log2(e)/sqrt(head dim) (attn_pipe_kernel with q_prescaled: no per-query scaling pass; one 16-bit rounding of Q
+// instead of two)
+inline void prescale_item_q(std::vector<float>& w, size_t nq, int head_dim) {
+  const float qsc = 1.4426950408889634f / std::sqrt((float)head_dim);
+  for (size_t i = 0; i < nq; ++i) w[i] *= qsc;
+}
+
+// one MGM head's W1 [D][D] and bias [D]: the GLU halves a = rows [0, D/2), b = rows [D/2, D) interleaved in
+// 16-row blocks, [a 16i..16i+15 | b 16i..16i+15] per 32 output rows
+inline void glu_interleave(std::vector<float>& W, std::vector<float>& B, int D) {
+  const std::vector<float> w = W, c = B;
+  for (int i = 0; i < D / 32; ++i)
+    for (int r = 0; r < 32; ++r) {
+      const int src = r < 16 ? 16 * i + r : D / 2 + 16 * i + (r - 16), dst = 32 * i + r;
+      std::memcpy(&W[(size_t)dst * D], &w[(size_t)src * D], D * sizeof(float));
+      B[dst] = c[src];
+    }
+}
+
+// CAP's weight-only query path in_proj_q(q_proj(q_norm(queries))) (transformer.py:81), accumulated in double:
+// queries [cap][E], q_norm affine g / b [E], q_proj weight qpw [E][E] (no bias), the MHA in-projection's Q rows
+// inw [E][E] and bias inb [E] -> [cap][E]
+inline std::vector<float> cap_query_path(const float* queries, const float* g, const float* b, const float* qpw,
+                                         const float* inw, const float* inb, int cap, int E, float ln_eps) {
+  std::vector<float> qp((size_t)cap * E);
+  std::vector<double> qn(E), qq(E);
+  for (int c = 0; c < cap; ++c) {
+    const float* q = queries + (size_t)c * E;
+    double mu = 0, var = 0;
+    for (int e = 0; e < E; ++e) mu += q[e];
+    mu /= E;
+    for (int e = 0; e < E; ++e) var += (q[e] - mu) * (q[e] - mu);
+    var /= E;
+    const double inv = 1.0 / std::sqrt(var + ln_eps);
+    for (int e = 0; e < E; ++e) qn[e] = (q[e] - mu) * inv * g[e] + b[e];
+    for (int o = 0; o < E; ++o) {
+      double a = 0;
+      for (int e = 0; e < E; ++e) a += qpw[(size_t)o * E + e] * qn[e];
+      qq[o] = a;
+    }
+    for (int o = 0; o < E; ++o) {
+      double a = inb[o];
+      for (int e = 0; e < E; ++e) a += inw[(size_t)o * E + e] * qq[e];
+      qp[(size_t)c * E + o] = (float)a;
+    }
+  }
+  return qp;
+}
+
 // w_out [H][d][E] -> W[e][h*d+dd]
 inline std::vector<float> transpose_out(const std::vector<float>& w, int HD, int E) {
   std::vector<float> o((size_t)E * HD);

@@ -51,6 +51,34 @@ int main(int argc, char** argv) {
     for (size_t i = 0; i < bits.size(); ++i) hout[i] = f2h(fin[i]);
     ok &= dump(dir, "f2h_out.bin", hout);
   }
+  ok &= dump(dir, "split_bf16.bin", split_bf16(fin));  // parity-mode planes [hi | lo] of the same inputs
+  for (int D : {192, 768}) {  // GLU interleave of one MGM head: W1 [D][D] and its bias on iota inputs
+    std::vector<float> W = iota_f((size_t)D * D), B = iota_f(D);
+    glu_interleave(W, B, D);
+    const std::string n = std::to_string(D);
+    ok &= dump(dir, ("glu_W" + n + ".bin").c_str(), W) && dump(dir, ("glu_B" + n + ".bin").c_str(), B);
+  }
+  {  // CAP's weight-only query path at cap = 4 on seeded weights, written with its inputs
+    const int cap = 4;
+    uint32_t s = 12345u;
+    auto fillr = [&](size_t n, float scale, float shift) {
+      std::vector<float> v(n);
+      for (float& x : v) s = s * 1664525u + 1013904223u, x = ((float)(s >> 8) / 16777216.0f - 0.5f) * scale + shift;
+      return v;
+    };
+    const std::vector<float> q = fillr((size_t)cap * E, 2.0f, 0.1f), g = fillr(E, 0.5f, 1.0f), b = fillr(E, 0.2f, 0.0f),
+                             qpw = fillr((size_t)E * E, 0.25f, 0.0f), inw = fillr((size_t)E * E, 0.25f, 0.0f),
+                             inb = fillr(E, 0.2f, 0.0f);
+    ok &= dump(dir, "capq_q.bin", q) && dump(dir, "capq_g.bin", g) && dump(dir, "capq_b.bin", b);
+    ok &= dump(dir, "capq_qpw.bin", qpw) && dump(dir, "capq_inw.bin", inw) && dump(dir, "capq_inb.bin", inb);
+    ok &= dump(dir, "capq_out.bin",
+               cap_query_path(q.data(), g.data(), b.data(), qpw.data(), inw.data(), inb.data(), cap, E, 1e-5f));
+  }
+  {  // item-Q prescale: the first 32 of 64 elements by log2(e)/sqrt(32)
+    std::vector<float> w = iota_f(64);
+    prescale_item_q(w, 32, 32);
+    ok &= dump(dir, "prescale_q.bin", w);
+  }
   ok &= dump(dir, "transpose_out.bin", transpose_out(iota_f((size_t)E * E), E, E));
   ok &= dump(dir, "rows_f16.bin", permute_rows_f16(iota_f((size_t)E * Fh), E, Fh));
   ok &= dump(dir, "mlp1.bin", pack_mlp1_perm(iota_f((size_t)Fh * E), E, Fh));

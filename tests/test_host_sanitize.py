@@ -3,7 +3,8 @@
 ``tests/native/host_check.cpp`` runs the engine's host code on the model's real shapes, built with
 ``g++ -fsanitize=address,undefined -fno-sanitize-recover=all``:
 * the weight packing of ``mmpfn_finalize_weights`` (``csrc/weight_pack.h``): bf16 rounding, the out-projection
-  transpose, the MLP K / hidden permutations, the feature-block LDS images, the LayerNorm fold;
+  transpose, the MLP K / hidden permutations, the feature-block LDS images, the LayerNorm fold, the parity mode's
+  hi | lo planes, the MGM GLU interleave, the CAP query path, the item-Q prescale;
 * ``mmpfn_siphash24_rows`` (``csrc/host.cpp``), the fingerprint feature's row hash.
 Any sanitizer report aborts the binary.  Its outputs are compared here with independent restatements
 (numpy index arithmetic from the layouts the kernels document, torch's bf16 conversion, the numpy SipHash).
@@ -70,6 +71,59 @@ def test_f2h_matches_torch(outputs):
     nan = np.isnan(bits.view(np.float32))
     assert np.array_equal(mine[~nan], ref[~nan])
     assert np.all((mine[nan] & 0x7C00) == 0x7C00) and np.all((mine[nan] & 0x03FF) != 0)
+
+
+def test_split_bf16_planes(outputs):
+    """Parity-mode weight planes: hi = bf16(x), lo = bf16(x - hi), the lo plane numel elements after the hi one."""
+    bits = outputs("f2bf_in.bin", np.uint32)
+    planes = outputs("split_bf16.bin", np.uint16)
+    assert planes.size == 2 * bits.size
+    x = torch.from_numpy(bits.view(np.float32).copy())
+    ok = ~np.isnan(bits.view(np.float32))
+    hi = x.to(torch.bfloat16)
+    lo = (x - hi.float()).to(torch.bfloat16)
+    lo_ok = ok & ~np.isinf(bits.view(np.float32))  # x = +-inf: lo = inf - inf is a NaN, no value to compare
+    assert not torch.isnan(lo.float()).numpy()[lo_ok].any() and (ok & ~lo_ok).sum() == 2
+
+    def as_u16(t):
+        return t.view(torch.int16).numpy().view(np.uint16)
+
+    assert np.array_equal(planes[:bits.size][ok], as_u16(hi)[ok])
+    assert np.array_equal(planes[bits.size:][lo_ok], as_u16(lo)[lo_ok])
+
+
+@pytest.mark.parametrize("D", [192, 768])
+def test_glu_interleave(outputs, D):
+    """Per 32 output rows: a[16i..16i+15] | b[16i..16i+15], a = rows [0, D/2), b = rows [D/2, D)."""
+    r = np.arange(D)
+    i, k = r // 32, r % 32
+    src = np.where(k < 16, 16 * i + k, D // 2 + 16 * i + (k - 16))
+    assert sorted(src.tolist()) == list(range(D))
+    w = np.arange(D * D, dtype=np.float32).reshape(D, D)
+    assert np.array_equal(outputs(f"glu_W{D}.bin", np.float32).reshape(D, D), w[src])
+    assert np.array_equal(outputs(f"glu_B{D}.bin", np.float32), np.arange(D, dtype=np.float32)[src])
+
+
+def test_cap_query_path(outputs):
+    """in_proj_q(q_proj(q_norm(queries))) at cap = 4, E = 192 against float64 numpy: both sides accumulate in double,
+    so they differ only where the exact value lies next to an fp32 rounding boundary -- at most 1 ulp of fp32."""
+    cap = 4
+    q = outputs("capq_q.bin", np.float32).reshape(cap, E).astype(np.float64)
+    g, b, inb = (outputs(f"capq_{n}.bin", np.float32).astype(np.float64) for n in ("g", "b", "inb"))
+    qpw, inw = (outputs(f"capq_{n}.bin", np.float32).reshape(E, E).astype(np.float64) for n in ("qpw", "inw"))
+    mu = q.mean(1, keepdims=True)
+    var = ((q - mu) ** 2).mean(1, keepdims=True)
+    qn = (q - mu) / np.sqrt(var + np.float64(np.float32(1e-5))) * g + b
+    ref = ((qn @ qpw.T) @ inw.T + inb).astype(np.float32)
+    got = outputs("capq_out.bin", np.float32).reshape(cap, E)
+    assert np.all(np.isfinite(got)) and np.abs(ref).max() > 0.1
+    assert np.all(np.abs(got - ref) <= np.spacing(np.abs(ref)))
+
+
+def test_prescale_item_q(outputs):
+    w = np.arange(64, dtype=np.float32)
+    w[:32] *= np.float32(1.4426950408889634) / np.sqrt(np.float32(32.0))
+    assert np.array_equal(outputs("prescale_q.bin", np.float32), w)
 
 
 def _f16_row_perm(r):  # tile f row 4g+i <- feature 32(f>>1) + 8g + 4(f&1) + i
