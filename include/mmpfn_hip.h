@@ -78,13 +78,13 @@ typedef struct mmpfn_model_desc {
   int emsize;             /* E = 192 */
   int nhead;              /* 6 (head dim must be 32) */
   int nlayers;            /* 12 */
-  int nhid;               /* 768 (MLP hidden, decoder hidden, modality width) */
+  int nhid;               /* 768 (MLP hidden, decoder hidden, modality width); with a mixer a multiple of 384 */
   int features_per_group; /* model grouping (yaml) */
   int encoder_features;   /* encoder width nf (checkpoint config.features_per_group) */
   int n_out;              /* decoder outputs (10) */
   int mixer_type;         /* MMPFN_MIXER_* */
   int mgm_heads;          /* MGM heads, or MoE experts */
-  int cap_heads;          /* CAP queries/heads */
+  int cap_heads;          /* CAP queries/heads: a divisor of 192 other than 1 */
   int two_sets_of_queries;
   int remove_duplicate_features; /* encoder Linear step index 6 instead of 5 */
   float ln_eps;           /* 1e-5 */
@@ -98,7 +98,14 @@ const char* mmpfn_last_error(const mmpfn_ctx* ctx);
 int mmpfn_set_stream(mmpfn_ctx* ctx, void* hip_stream);
 const char* mmpfn_version(void);
 
-/* ---- weights (checkpoint ABI: reference state_dict names, fp32 host data) -------- */
+/* ---- weights (checkpoint ABI: reference state_dict names, fp32 host data) --------
+ * mmpfn_set_model is the one place that checks the model: a geometry that some kernel behind it cannot run is
+ * refused here with MMPFN_ERR_INVALID (mmpfn_last_error names the field), never by a launch in a forward:
+ *   emsize 192 in 6 heads of 32; nhid a multiple of 192, and with a mixer a multiple of 384 (nhid / 2, the
+ *   modality heads' down-projection depth, must be a multiple of 64: nhid 192 and 576 are refused);
+ *   nlayers, n_out >= 1; 1 <= features_per_group <= encoder_features <= 8;
+ *   MGM+CAP: cap_heads a divisor of 192 other than 1 (head dims 96 .. 1 have a CAP attention kernel, head dim 192
+ *   has none: cap_heads 1 is refused). */
 int mmpfn_set_model(mmpfn_ctx* ctx, const mmpfn_model_desc* desc);
 int mmpfn_load_weight(mmpfn_ctx* ctx, const char* name, const float* host_data, int64_t numel);
 int mmpfn_finalize_weights(mmpfn_ctx* ctx); /* pack / fold / convert / upload; synchronous */

@@ -937,8 +937,10 @@ int mmpfn_set_stream(mmpfn_ctx* ctx, void* stream) {
 }
 
 // The engine's model contract, checked here and nowhere else: emsize E = 192 in six heads of 32, and an MLP / image
-// width nhid that is a multiple of 192.  Everything behind a finalised model relies on it -- the row-resident
-// kernels (featrow, rowgemm, rowgemm3, mlp_rows) and the MGM big-tile GEMMs always apply, and the dispatch below
+// width nhid that is a multiple of 192 -- with a mixer, of 384 (nhid / 2, the head banks' down-projection K, a
+// multiple of 64) -- and for MGM+CAP a cap_heads whose head dim E / cap_heads the CAP attention is instantiated for
+// (cap_head_dim_supported: every divisor of 192 but 1).  Everything behind a finalised model relies on it -- the
+// row-resident kernels (featrow, rowgemm, rowgemm3, mlp_rows) and the MGM big-tile GEMMs always apply, and the dispatch below
 // branches only on what still varies: the precision mode, T <= 64, mgm_heads * nhid % 256, the 16-bit decoder's
 // n_out <= 16 && nhid % 128 == 0, and the CAP MFMA shape (24 heads, M % 32 == 0, M <= 128).
 int mmpfn_set_model(mmpfn_ctx* ctx, const mmpfn_model_desc* desc) {
@@ -949,8 +951,16 @@ int mmpfn_set_model(mmpfn_ctx* ctx, const mmpfn_model_desc* desc) {
   if (d.nhid % 192 != 0 || d.nlayers <= 0 || d.features_per_group <= 0 || d.features_per_group > 8 ||
       d.encoder_features < d.features_per_group || d.encoder_features > 8 || d.n_out <= 0)
     return fail(ctx, MMPFN_ERR_INVALID, "unsupported model geometry");
+  // the head banks' down-projection contracts over K = nhid / 2, in 64-wide slices in the bf16 and split-bf16 GEMMs
+  if (d.mixer_type != MMPFN_MIXER_NONE && (d.nhid / 2) % 64 != 0)
+    return fail(ctx, MMPFN_ERR_INVALID,
+                "nhid " + std::to_string(d.nhid) + ": a model with a mixer needs nhid / 2 to be a multiple of 64");
   if (d.mixer_type == MMPFN_MIXER_MGM_CAP && (d.cap_heads <= 0 || d.emsize % d.cap_heads != 0))
     return fail(ctx, MMPFN_ERR_INVALID, "cap_heads must divide emsize");
+  if (d.mixer_type == MMPFN_MIXER_MGM_CAP && !cap_head_dim_supported(d.emsize / d.cap_heads))
+    return fail(ctx, MMPFN_ERR_INVALID,
+                "cap_heads " + std::to_string(d.cap_heads) + ": the CAP attention has no kernel for head dim " +
+                    std::to_string(d.emsize / d.cap_heads));
   ctx->d = d;
   ctx->have_model = true;
   ctx->finalized = false;

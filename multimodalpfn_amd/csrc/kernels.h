@@ -281,7 +281,9 @@ hipError_t launch_aggregate(const float* logits /*[M][Q][n_out]*/, int M, int Q,
 // ---- mixer helpers -----------------------------------------------------------------
 hipError_t launch_layernorm_rows(const float* in, int64_t rows, int dim, float eps, void* out, DType out_t,
                                  const float* gamma, const float* beta, hipStream_t st);
-// kv and out both fp32 (the fp32 modes) or both bf16
+// whether the CAP attention has a kernel for head dim hd = E / cap_heads (mixer.hip CapDims, the one list)
+bool cap_head_dim_supported(int hd);
+// kv and out both fp32 (the fp32 modes) or both bf16; hipErrorInvalidValue unless cap_head_dim_supported(E / cap)
 hipError_t launch_cap_attention(const float* qp /*[cap][E]*/, const void* kv /*[S][M][2E]*/, DType kv_t,
                                 void* out /*[S][cap][E]*/, DType out_t, int S, int M, int cap, int E, hipStream_t st);
 // CAP core on MFMA (bf16; head dim 8, 24 heads = cap queries, M % 32 == 0, M <= 128): K [S*M][E], V^T [S][E][M]

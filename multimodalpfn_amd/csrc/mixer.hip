@@ -359,6 +359,33 @@ hipError_t launch_layernorm_rows(const float* in, int64_t rows, int dim, float e
   return hipGetLastError();
 }
 
+// The head dims (E / cap_heads) cap_attn_kernel is instantiated for, stated once: launch_cap_t dispatches over this
+// list and cap_head_dim_supported (mmpfn_set_model's check) answers from it.  At E = 192: cap_heads 2, 3, 4, 6, 8,
+// 12, 16, 24, 32, 48, 64, 96 and 192.  Head dim 192 (cap_heads 1) is left out: two 192-float register arrays per
+// thread at 1024 threads a block would live in scratch, and no reference configuration uses it.
+template <int... HD>
+struct CapHeadDims {};
+using CapDims = CapHeadDims<96, 64, 48, 32, 24, 16, 12, 8, 6, 4, 3, 2, 1>;
+
+template <int... HD>
+bool cap_dims_have(CapHeadDims<HD...>, int hd) {
+  return ((hd == HD) || ...);
+}
+
+template <typename TK, typename TO, int HD>
+bool cap_launch_if(int hd, dim3 g, dim3 b, size_t lds, hipStream_t st, const float* qp, const TK* kv, TO* out, int M,
+                   int cap, int E, int kcmax) {
+  if (hd != HD) return false;
+  hipLaunchKernelGGL((cap_attn_kernel<TK, TO, HD>), g, b, lds, st, qp, kv, out, M, cap, E, kcmax);
+  return true;
+}
+
+template <typename TK, typename TO, int... HD>
+bool cap_dispatch(CapHeadDims<HD...>, int hd, dim3 g, dim3 b, size_t lds, hipStream_t st, const float* qp,
+                  const TK* kv, TO* out, int M, int cap, int E, int kcmax) {
+  return (cap_launch_if<TK, TO, HD>(hd, g, b, lds, st, qp, kv, out, M, cap, E, kcmax) || ...);
+}
+
 template <typename TK, typename TO>
 hipError_t launch_cap_t(const float* qp, const TK* kv, TO* out, int S, int M, int cap, int E, hipStream_t st) {
   // the row's keys staged in their storage type, chunks of up to 64 keys within 96 KiB of LDS
@@ -367,22 +394,12 @@ hipError_t launch_cap_t(const float* qp, const TK* kv, TO* out, int S, int M, in
   const size_t lds = (size_t)kcmax * 2 * E * sizeof(TK);
   const int pairs = cap * cap;
   dim3 g(S), b((unsigned)min(1024, (pairs + 63) / 64 * 64));
-  switch (E / cap) {
-    case 96: hipLaunchKernelGGL((cap_attn_kernel<TK, TO, 96>), g, b, lds, st, qp, kv, out, M, cap, E, kcmax); break;
-    case 48: hipLaunchKernelGGL((cap_attn_kernel<TK, TO, 48>), g, b, lds, st, qp, kv, out, M, cap, E, kcmax); break;
-    case 24: hipLaunchKernelGGL((cap_attn_kernel<TK, TO, 24>), g, b, lds, st, qp, kv, out, M, cap, E, kcmax); break;
-    case 16: hipLaunchKernelGGL((cap_attn_kernel<TK, TO, 16>), g, b, lds, st, qp, kv, out, M, cap, E, kcmax); break;
-    case 12: hipLaunchKernelGGL((cap_attn_kernel<TK, TO, 12>), g, b, lds, st, qp, kv, out, M, cap, E, kcmax); break;
-    case 8: hipLaunchKernelGGL((cap_attn_kernel<TK, TO, 8>), g, b, lds, st, qp, kv, out, M, cap, E, kcmax); break;
-    case 6: hipLaunchKernelGGL((cap_attn_kernel<TK, TO, 6>), g, b, lds, st, qp, kv, out, M, cap, E, kcmax); break;
-    case 4: hipLaunchKernelGGL((cap_attn_kernel<TK, TO, 4>), g, b, lds, st, qp, kv, out, M, cap, E, kcmax); break;
-    case 3: hipLaunchKernelGGL((cap_attn_kernel<TK, TO, 3>), g, b, lds, st, qp, kv, out, M, cap, E, kcmax); break;
-    case 2: hipLaunchKernelGGL((cap_attn_kernel<TK, TO, 2>), g, b, lds, st, qp, kv, out, M, cap, E, kcmax); break;
-    case 1: hipLaunchKernelGGL((cap_attn_kernel<TK, TO, 1>), g, b, lds, st, qp, kv, out, M, cap, E, kcmax); break;
-    default: return hipErrorInvalidValue;  // cap_heads with E / cap outside the instantiated set
-  }
+  if (!cap_dispatch(CapDims{}, E / cap, g, b, lds, st, qp, kv, out, M, cap, E, kcmax))
+    return hipErrorInvalidValue;  // a head dim outside CapDims: mmpfn_set_model refuses such a model
   return hipGetLastError();
 }
+
+bool cap_head_dim_supported(int hd) { return cap_dims_have(CapDims{}, hd); }
 
 hipError_t launch_cap_attention(const float* qp, const void* kv, DType kv_t, void* out, DType out_t, int S, int M,
                                 int cap, int E, hipStream_t st) {

@@ -7,7 +7,8 @@ lacks, since the dispatch branches on a form's presence:
 * model A has both optional forms: the 16-bit MFMA decoder (``n_out <= 16 and nhid % 128 == 0``: n_out = 10,
   nhid = 768) and the fp16 MGM head bank (``mgm_heads * nhid % 256 == 0``: 4 heads);
 * model B has neither: n_out = 17, and one MGM head of nhid = 384 (384 % 256 != 0).  (nhid = 192 would lose the
-  decoder form too, but PREC_F32 refuses it: the head bank's down-projection then has K = 96, not a multiple of 64.)
+  decoder form too, but ``mmpfn_set_model`` refuses a mixer model of that width: the head bank's down-projection
+  then has K = 96, not a multiple of 64; tests/test_mixer_gpu.py.)
 
 Mixer tokens and logits of B on the re-finalised context must be ``torch.equal`` to a fresh engine's, in every base
 precision mode.  Two engines, one process; S = 48, N = 32, F = 4, one modality.
