@@ -925,14 +925,10 @@ hipError_t launch_item_attention(const AttnLayerArgs& l, bool x3, hipStream_t st
 
 }  // namespace
 
-hipError_t launch_attn_layer(const AttnLayerArgs& a, hipStream_t st) { return launch_item_attention(a, false, st); }
-
 int set_x3_cheap_min_keys(int n, int form) {
   if (form >= 1 && form <= 3) g_x3_cheap_form.store(form);
   return g_x3_cheap_min_keys.exchange(n);
 }
-
-hipError_t launch_attn_item3(const AttnLayerArgs& a, hipStream_t st) { return launch_item_attention(a, true, st); }
 
 hipError_t launch_attn(const AttnArgs& a, int batches, int prec, int nw, hipStream_t st) {
   if (a.nq <= 0 || batches <= 0) return hipSuccess;
@@ -946,7 +942,7 @@ hipError_t launch_attn(const AttnArgs& a, int batches, int prec, int nw, hipStre
   if (a.nk <= 0 || a.kpad % IA_KT != 0 || a.nk > a.kpad) return hipErrorInvalidValue;
   if (nw != 1 && nw != 4) return hipErrorInvalidValue;
   dim3 grid((a.nq + 32 * nw - 1) / (32 * nw), a.H, batches);
-  // four waves per block: PREC_F32_MFMA's item attention only (launch_attn_item; the other modes' item attention
+  // four waves per block: PREC_F32_MFMA's item attention only (launch_attn_layer; the other modes' item attention
   // runs launch_item_attention)
   if (nw == 4 && prec != PREC_F32_MFMA) return hipErrorInvalidValue;
   if (prec == PREC_BF16) {
@@ -960,24 +956,29 @@ hipError_t launch_attn(const AttnArgs& a, int batches, int prec, int nw, hipStre
   return hipGetLastError();
 }
 
-hipError_t launch_attn_item(const void* q, const void* k, const void* vt, void* out, int S, int T, int H, int Npad,
-                            int s0, int nq, int nk, int kv_head_fixed, int prec, hipStream_t st, int64_t kv_bstride) {
+hipError_t launch_attn_layer(const AttnLayerArgs& l, int base_prec, hipStream_t st) {
+  if (prec16(base_prec) || base_prec == PREC_F32) return launch_item_attention(l, base_prec == PREC_F32, st);
+  if (base_prec != PREC_F32_MFMA) return hipErrorInvalidValue;
+  if (l.nb > 0 && (l.kvb < 0 || l.kvb >= l.H)) return hipErrorInvalidValue;
   AttnArgs a;
-  a.q = q, a.k = k, a.vt = vt, a.o = out;
-  a.q_bstride = (int64_t)H * S * 32, a.q_hstride = (int64_t)S * 32;
-  a.kv_bstride = kv_bstride > 0 ? kv_bstride : (int64_t)H * Npad * 32, a.kv_hstride = (int64_t)Npad * 32;
-  a.kpad = Npad;
-  if (kv_bstride > 0 && kv_head_fixed != 0) return hipErrorInvalidValue;
-  a.o_bstride = S, a.o_qstride = 1;
-  a.s0 = s0, a.nq = nq, a.nk = nk, a.kvh_fixed = kv_head_fixed, a.H = H;
-  if (prec == PREC_BF16 || prec == PREC_F32) {
-    AttnLayerArgs l{q, k, vt, out, S, T, H, Npad, nk};
-    if (kv_head_fixed < 0) l.a0 = s0, l.na = nq, l.b0 = 0, l.nb = 0, l.kvb = -1;
-    else l.a0 = 0, l.na = 0, l.b0 = s0, l.nb = nq, l.kvb = kv_head_fixed;
-    l.kv_bstride = kv_bstride;
-    return launch_item_attention(l, prec == PREC_F32, st);
+  a.q = l.q, a.k = l.k, a.vt = l.vt, a.o = l.out;
+  a.q_bstride = (int64_t)l.H * l.S * 32, a.q_hstride = (int64_t)l.S * 32;
+  a.kv_bstride = l.kv_bstride > 0 ? l.kv_bstride : (int64_t)l.H * l.Npad * 32, a.kv_hstride = (int64_t)l.Npad * 32;
+  a.kpad = l.Npad;
+  a.o_bstride = l.S, a.o_qstride = 1;
+  a.nk = l.nk, a.H = l.H;
+  if (l.na > 0) {  // own heads
+    if (l.kv_bstride > 0) return hipErrorInvalidValue;  // cache layout holds head 0 only
+    a.s0 = l.a0, a.nq = l.na, a.kvh_fixed = -1;
+    const hipError_t e = launch_attn(a, l.T, PREC_F32_MFMA, 4, st);
+    if (e != hipSuccess) return e;
   }
-  return launch_attn(a, T, prec, 4, st);
+  if (l.nb > 0) {  // every head against K/V head kvb
+    if (l.kv_bstride > 0 && l.kvb != 0) return hipErrorInvalidValue;
+    a.s0 = l.b0, a.nq = l.nb, a.kvh_fixed = l.kvb;
+    return launch_attn(a, l.T, PREC_F32_MFMA, 4, st);
+  }
+  return hipSuccess;
 }
 
 }  // namespace mmpfn

@@ -293,15 +293,6 @@ int finalize(mmpfn_ctx* ctx) {
   return MMPFN_OK;
 }
 
-// parity-mode row-resident projections (rowgemm3.hip) on the split planes of w
-Proj3Set p3set(const Weight& w, const float* A, int64_t rdiv, int64_t rmul, int64_t rmul2, int64_t roff, int64_t M,
-               int N) {
-  return Proj3Set{A, rdiv, rmul, rmul2, roff, w.split.p, w.numel, (int)M, N};
-}
-hipError_t p3_resln(const mmpfn_ctx* ctx, const Weight& w, const void* O, int64_t M, float* X, hipStream_t st) {
-  return launch_proj3_resln((const float*)O, w.split.p, w.numel, M, X, ctx->d.ln_eps, st);
-}
-
 GemmArgs gargs() {
   GemmArgs a;
   std::memset(&a, 0, sizeof(a));
@@ -339,6 +330,60 @@ PrecMode decode_prec(int code, int T) {
   return m;
 }
 PrecMode lane_prec(const Lane& l) { return PrecMode{l.prec, l.f8}; }
+
+// ---- The steps of a layer that every mode runs on a kernel family of its own: the q|k|v projection and the
+//      out-projection + residual + LayerNorm here, the item attention behind launch_attn_layer(a, pm.base), the MLP in
+//      mlp_sublayer.  Precision meets kernel family in these and nowhere else in the layer path.
+//      rows16: the 16-bit modes run their row-resident kernels (rowgemm.hip); false (the feature attention of tables
+//      wider than featrow.hip's 64 tokens): the generic bf16 GEMM on the fp32 state.
+struct QkvRows {  // r's rows of X through w; project_qkv fills r.W / r.w_lo in the mode's form
+  const Weight& w;
+  RowSet r;
+};
+// X's row sets (one or two) -> Q [b][H][pos][32], K [b][H][pos][32] (Npad rows), V^T [b][H][32][Npad]; S: rows of Q
+int project_qkv(mmpfn_ctx* ctx, PrecMode pm, bool rows16, const void* X, const QkvRows* sets, int nset, void* Q,
+                void* K, void* Vt, int S, int Npad, int H) {
+  hipStream_t st = ctx->stream;
+  RowSet rs[2];
+  if (nset < 1 || nset > 2) return fail(ctx, MMPFN_ERR_INVALID, "project_qkv: one or two row sets");
+  for (int i = 0; i < nset; ++i) rs[i] = sets[i].r;
+  if (pm.is16() && rows16) {
+    for (int i = 0; i < nset; ++i) rs[i].W = sets[i].w.op16(pm.w16());
+    HIPCHK(launch_rowgemm_qkv(X, rs, nset, Q, K, Vt, S, Npad, H, st, pm.state(), pm.qk()));
+  } else if (pm.base == PREC_F32) {  // parity mode: split-bf16 products, every set in one launch (rowgemm3.hip)
+    for (int i = 0; i < nset; ++i) rs[i].W = sets[i].w.split.p, rs[i].w_lo = sets[i].w.numel;
+    HIPCHK(launch_proj3_qkv((const float*)X, rs, nset, Q, K, Vt, S, Npad, H, st));
+  } else {
+    for (int i = 0; i < nset; ++i) {
+      const RowSet& r = rs[i];
+      if (r.M <= 0) continue;
+      GemmArgs a = gargs();
+      a.A = X, a.lda = ctx->d.emsize, a.a_rdiv = r.rdiv, a.a_rmul = r.rmul, a.a_rmul2 = r.rmul2, a.a_roff = r.roff;
+      sets[i].w.gemm_operand(a, pm.gemm());
+      a.M = r.M, a.N = r.N, a.K = ctx->d.emsize;
+      a.q = Q, a.k = K, a.v = Vt, a.S = S, a.Npad = Npad, a.T = (int)(r.M / r.rdiv), a.H = H;
+      HIPCHK(launch_gemm(a, pm.gemm(), EPI_ITEM_QKV, true, !pm.is16(), 1, st));
+    }
+  }
+  return MMPFN_OK;
+}
+
+// X <- LN(X + O W^T) over `rows` tokens (O: an attention output, W: its out-projection)
+int out_proj_ln(mmpfn_ctx* ctx, PrecMode pm, bool rows16, const Weight& W, const void* O, void* X, int64_t rows) {
+  const mmpfn_model_desc& d = ctx->d;
+  hipStream_t st = ctx->stream;
+  if (pm.is16() && rows16) {
+    HIPCHK(launch_rowgemm_resln(O, W.op16(pm.w16()), rows, X, d.ln_eps, st, pm.state()));
+  } else if (pm.base == PREC_F32) {
+    HIPCHK(launch_proj3_resln((const float*)O, W.split.p, W.numel, rows, (float*)X, d.ln_eps, st));
+  } else {  // (bf16: O bf16, X fp32)
+    GemmArgs b = gargs();
+    b.A = O, b.lda = d.emsize, W.gemm_operand(b, pm.gemm());
+    b.M = (int)rows, b.N = d.emsize, b.K = d.emsize, b.X = (float*)X, b.ln_eps = d.ln_eps;
+    HIPCHK(launch_gemm(b, pm.gemm(), EPI_RES_LN, !pm.is16(), true, 1, st));
+  }
+  return MMPFN_OK;
+}
 
 // the selected lane's workspaces for M members of S x T tokens with Npad padded train rows: ws_X (own_state; a tap
 // runs on the caller's) and ws_O hold the state and the attention output, ws_big the Q / K / V^T of the feature
@@ -427,37 +472,26 @@ int feat_sublayer(mmpfn_ctx* ctx, const LayerW& L, void* Xv, int S, int T, int M
   const mmpfn_model_desc& d = ctx->d;
   const int E = d.emsize, H = d.nhead;
   const int64_t R = (int64_t)S * T;
-  const bool b16 = pm.is16();
   const int eb = pm.op_bytes();
   hipStream_t st = ctx->stream;
   void* O = ctx->ws_O.p;
   unsigned char* big = (unsigned char*)ctx->ws_big.p;
-  if (b16 && T <= 64) {
+  if (pm.is16() && T <= 64) {
     // one wave per row (all M members' rows in one launch), the whole sublayer in registers (featrow.hip); an
     // fp16 state always comes here (decode_prec keeps PREC_F16 to T <= 64)
     HIPCHK(launch_feat_rows(Xv, L.feat_pack.op16(pm.w16()), S, T, M, E, H, d.ln_eps, st, pm.state(),
                             last));
     return MMPFN_OK;
   }
-  float* Xall = (float*)Xv;
+  const int Tpad = (T + 63) / 64 * 64;
+  void* Qf = big;
+  void* Kf = big + (size_t)R * E * eb;
+  void* Vf = (unsigned char*)Kf + (size_t)S * H * Tpad * 32 * eb;
   for (int m = 0; m < M; ++m) {  // member by member (the scratch holds one member)
-    float* X = Xall + (size_t)m * R * E;
-    const int Tpad = (T + 63) / 64 * 64;
-    void* Qf = big;
-    void* Kf = big + (size_t)R * E * eb;
-    void* Vf = (unsigned char*)Kf + (size_t)S * H * Tpad * 32 * eb;
+    float* X = (float*)Xv + (size_t)m * R * E;
     // logical rows m = s*T + t: A row t*S + s; scatter batch b = s, position t
-    if (pm.base == PREC_F32) {
-      const Proj3Set ps = p3set(L.feat_qkv, X, T, 1, S, 0, R, 3 * E);
-      HIPCHK(launch_proj3_qkv(&ps, 1, Qf, Kf, Vf, T, Tpad, H, st));
-    } else {
-      GemmArgs a = gargs();
-      a.A = X, a.lda = E, a.a_rdiv = T, a.a_rmul = 1, a.a_rmul2 = S;
-      L.feat_qkv.gemm_operand(a, pm.gemm());
-      a.M = (int)R, a.N = 3 * E, a.K = E;
-      a.q = Qf, a.k = Kf, a.v = Vf, a.S = T, a.Npad = Tpad, a.T = T, a.H = H;
-      HIPCHK(launch_gemm(a, pm.gemm(), EPI_ITEM_QKV, true, !b16, 1, st));
-    }
+    const QkvRows rows{L.feat_qkv, {T, 1, S, 0, (int)R, 3 * E}};
+    RC(project_qkv(ctx, pm, false, X, &rows, 1, Qf, Kf, Vf, T, Tpad, H));
     AttnArgs f;
     f.q = Qf, f.k = Kf, f.vt = Vf, f.o = O;
     f.q_bstride = (int64_t)H * T * 32, f.q_hstride = (int64_t)T * 32;
@@ -465,32 +499,7 @@ int feat_sublayer(mmpfn_ctx* ctx, const LayerW& L, void* Xv, int S, int T, int M
     f.o_bstride = 1, f.o_qstride = S;  // O[t][s]
     f.s0 = 0, f.nq = T, f.nk = T, f.kvh_fixed = -1, f.H = H;
     HIPCHK(launch_attn(f, S, pm.gemm(), 1, st));
-    if (pm.base == PREC_F32) {
-      HIPCHK(p3_resln(ctx, L.feat_out, O, R, X, st));
-      continue;
-    }
-    GemmArgs b = gargs();
-    b.A = O, b.lda = E, L.feat_out.gemm_operand(b, pm.gemm());
-    b.M = (int)R, b.N = E, b.K = E, b.X = X, b.ln_eps = d.ln_eps;
-    HIPCHK(launch_gemm(b, pm.gemm(), EPI_RES_LN, !b16, true, 1, st));
-  }
-  return MMPFN_OK;
-}
-
-// ---- the item attention's out-projection: X <- LN(X + O Wout^T) over RM tokens (O: the attention output)
-int item_out_proj(mmpfn_ctx* ctx, const LayerW& L, const void* O, void* Xv, int64_t RM, PrecMode pm) {
-  const mmpfn_model_desc& d = ctx->d;
-  const int E = d.emsize;
-  hipStream_t st = ctx->stream;
-  if (pm.is16()) {
-    HIPCHK(launch_rowgemm_resln(O, L.item_out.op16(pm.w16()), RM, Xv, d.ln_eps, st, pm.state()));
-  } else if (pm.base == PREC_F32) {
-    HIPCHK(p3_resln(ctx, L.item_out, O, RM, (float*)Xv, st));
-  } else {
-    GemmArgs b = gargs();
-    b.A = O, b.lda = E, L.item_out.gemm_operand(b, pm.base);
-    b.M = (int)RM, b.N = E, b.K = E, b.X = (float*)Xv, b.ln_eps = d.ln_eps;
-    HIPCHK(launch_gemm(b, pm.base, EPI_RES_LN, true, true, 1, st));
+    RC(out_proj_ln(ctx, pm, false, L.feat_out, O, X, R));
   }
   return MMPFN_OK;
 }
@@ -514,10 +523,6 @@ int item_sublayer(mmpfn_ctx* ctx, int l, void* Xv, int S, int T, int N, int Npad
   const int64_t cs = last ? (int64_t)T * S : S;  // state rows between consecutive columns
   const int c0 = last ? T - 1 : 0, nc = last ? 1 : T;  // the columns of one member, as the cache numbers them
   if (last) Xv = (char*)Xv + (size_t)(T - 1) * S * E * pm.state_bytes();
-  float* Xall = (float*)Xv;
-  // the 16-bit modes run the row-resident projections and the pipelined attention; PREC_F16 in their F16 forms
-  // (fp16 X and O, fp16 weight copies)
-  const bool b16 = pm.is16();
   const int eb = pm.op_bytes();
   hipStream_t st = ctx->stream;
   void* O = ctx->ws_O.p;
@@ -530,55 +535,18 @@ int item_sublayer(mmpfn_ctx* ctx, int l, void* Xv, int S, int T, int N, int Npad
     const size_t kvl = (size_t)T * cc->Npad * 32 * eb;
     const size_t ccol = (size_t)c0 * cc->Npad * 32 * eb;  // the first column's K (V^T) block inside the layer's
     const unsigned char* Kc = (const unsigned char*)cc->kv.p + (size_t)l * 2 * kvl + ccol;
-    const unsigned char* Vc = Kc + kvl;
-    if (b16) {
-      HIPCHK(launch_rowgemm_qkv(Xv, S, cs, 1, 0, L.item_qtest.op16(pm.w16()), TM * S, E, Qi, Ki, Vi, S,
-                                Npad, H, st, pm.state(), pm.qk()));
-    } else if (pm.base == PREC_F32) {
-      const Proj3Set ps = p3set(L.item_qtest, Xall, S, cs, 1, 0, (int64_t)TM * S, E);
-      HIPCHK(launch_proj3_qkv(&ps, 1, Qi, Ki, Vi, S, Npad, H, st));
-    } else {
-      GemmArgs c = gargs();
-      c.A = Xall, c.lda = E, c.a_rdiv = S, c.a_rmul = cs, c.a_roff = 0;
-      L.item_qtest.gemm_operand(c, pm.base);
-      c.M = TM * S, c.N = E, c.K = E;
-      c.q = Qi, c.k = Ki, c.v = Vi, c.S = S, c.Npad = Npad, c.T = TM, c.H = H;
-      HIPCHK(launch_gemm(c, pm.base, EPI_ITEM_QKV, true, true, 1, st));
-    }
-    const int64_t cstride = (int64_t)cc->Npad * 32;
-    if (b16) {
-      AttnLayerArgs a{Qi, Kc, Vc, O, S, TM, H, cc->Npad, cc->N};
-      a.a0 = 0, a.na = 0, a.b0 = 0, a.nb = S, a.kvb = 0;  // every row against head 0 of the cache
-      a.kv_bstride = cstride, a.q_prescaled = true, a.qk_t = pm.qk(), a.o_t = pm.attn_out();
-      HIPCHK(launch_attn_layer(a, st));
-    } else {
-      HIPCHK(launch_attn_item(Qi, Kc, Vc, O, S, TM, H, cc->Npad, 0, S, cc->N, 0, pm.base, st, cstride));
-    }
+    const QkvRows rows{L.item_qtest, {S, cs, 1, 0, TM * S, E}};
+    RC(project_qkv(ctx, pm, true, Xv, &rows, 1, Qi, Ki, Vi, S, Npad, H));
+    AttnLayerArgs a{Qi, Kc, Kc + kvl, O, S, TM, H, cc->Npad, cc->N};
+    a.a0 = 0, a.na = 0, a.b0 = 0, a.nb = S, a.kvb = 0;  // every row against head 0 of the cache
+    a.kv_bstride = (int64_t)cc->Npad * 32;
+    a.q_prescaled = pm.is16(), a.qk_t = pm.qk(), a.o_t = pm.attn_out();
+    HIPCHK(launch_attn_layer(a, pm.base, st));
   } else {
-    if (b16) {  // row-resident projections straight into the attention layouts
-      // train rows q|k|v and test rows q in one launch (test-row blocks last)
-      HIPCHK(launch_rowgemm_qkv_pair(Xv, N, 0, L.item_qkv.op16(pm.w16()), TM * N, 3 * E, Q, N,
-                                     L.item_qtest.op16(pm.w16()), TM * Q, E, cs, Qi, Ki, Vi, S, Npad, H, st,
-                                     pm.state(), pm.qk()));
-    } else if (pm.base == PREC_F32) {  // train rows q|k|v and test rows q in one launch
-      const Proj3Set ps[2] = {p3set(L.item_qkv, Xall, N, cs, 1, 0, (int64_t)TM * N, 3 * E),
-                              p3set(L.item_qtest, Xall, Q > 0 ? Q : 1, cs, 1, N, (int64_t)TM * Q, E)};
-      HIPCHK(launch_proj3_qkv(ps, 2, Qi, Ki, Vi, S, Npad, H, st));
-    } else {
-      GemmArgs a = gargs();
-      a.A = Xall, a.lda = E, a.a_rdiv = N, a.a_rmul = cs, a.a_roff = 0;
-      L.item_qkv.gemm_operand(a, pm.base);
-      a.M = TM * N, a.N = 3 * E, a.K = E;
-      a.q = Qi, a.k = Ki, a.v = Vi, a.S = S, a.Npad = Npad, a.T = TM, a.H = H;
-      HIPCHK(launch_gemm(a, pm.base, EPI_ITEM_QKV, true, true, 1, st));
-      if (Q > 0) {
-        GemmArgs c = a;
-        c.a_rdiv = Q, c.a_roff = N;
-        L.item_qtest.gemm_operand(c, pm.base);
-        c.M = TM * Q, c.N = E;
-        HIPCHK(launch_gemm(c, pm.base, EPI_ITEM_QKV, true, true, 1, st));
-      }
-    }
+    // train rows q|k|v and test rows q in one launch where the mode has one (test-row blocks last)
+    const QkvRows rows[2] = {{L.item_qkv, {N, cs, 1, 0, TM * N, 3 * E}},
+                             {L.item_qtest, {Q > 0 ? Q : 1, cs, 1, N, TM * Q, E}}};
+    RC(project_qkv(ctx, pm, true, Xv, rows, 2, Qi, Ki, Vi, S, Npad, H));
     if (ctx->cache_out) {  // keep head 0's K / V^T of every column (the test rows' KV, layer.py:344-358)
       mmpfn_cache* cc = ctx->cache_out;
       const size_t blk = (size_t)Npad * 32 * eb, kvl = (size_t)T * blk;
@@ -591,8 +559,9 @@ int item_sublayer(mmpfn_ctx* ctx, int l, void* Xv, int S, int T, int N, int Npad
     AttnLayerArgs a{Qi, Ki, Vi, O, S, TM, H, Npad, N};
     a.a0 = 0, a.na = N, a.b0 = N, a.nb = Q, a.kvb = 0;
     if (last) a.na = N % ATTN_ITEM_QPB, a.a0 = N - a.na;
-    if (b16) {  // in one launch
-      hipEvent_t* ev = nullptr;
+    a.q_prescaled = pm.is16(), a.qk_t = pm.qk(), a.o_t = pm.attn_out();
+    hipEvent_t* ev = nullptr;
+    if (pm.is16()) {  // the live timing and the fp8 P.V exist for the pipelined kernel only
       if (ctx->kt_on && !last) {  // (the roofline's launches all have the full layer's shape)
         if (ctx->kt_used + 2 > ctx->kt_pool.size()) {
           for (int i = 0; i < 64; ++i) {
@@ -610,19 +579,13 @@ int item_sublayer(mmpfn_ctx* ctx, int l, void* Xv, int S, int T, int N, int Npad
         HIPCHK(launch_vt_fp8(Vi, V8, (int64_t)TM * H * Npad * 32, st));
         a.vt8 = V8, a.f8 = pm.f8;
       }
-      a.q_prescaled = true, a.qk_t = pm.qk(), a.o_t = pm.attn_out();
-      if (ev) HIPCHK(hipEventRecord(ev[0], st));
-      HIPCHK(launch_attn_layer(a, st));
-      if (ev) HIPCHK(hipEventRecord(ev[1], st));
-    } else if (pm.base == PREC_F32) {  // parity mode: split-bf16 products, train and test rows in one launch
-      HIPCHK(launch_attn_item3(a, st));
-    } else {
-      if (!last) HIPCHK(launch_attn_item(Qi, Ki, Vi, O, S, TM, H, Npad, 0, N, N, -1, pm.base, st));
-      if (Q > 0) HIPCHK(launch_attn_item(Qi, Ki, Vi, O, S, TM, H, Npad, N, Q, N, 0, pm.base, st));
     }
+    if (ev) HIPCHK(hipEventRecord(ev[0], st));
+    HIPCHK(launch_attn_layer(a, pm.base, st));
+    if (ev) HIPCHK(hipEventRecord(ev[1], st));
   }
   if (fuse_out || last) return MMPFN_OK;
-  return item_out_proj(ctx, L, O, Xv, RM, pm);
+  return out_proj_ln(ctx, pm, true, L.item_out, O, Xv, RM);
 }
 
 // ---- MLP (mlp.py:93-104) + residual + LN over RM tokens; O non-null (the 16-bit modes): the item attention's
@@ -677,7 +640,7 @@ int last_layer_tail(mmpfn_ctx* ctx, int l) {
   for (int m = 0; m < M; ++m) {
     void* X = (char*)ctx->ws_X.p + (((size_t)m * T + T - 1) * S + N) * E * pm.state_bytes();
     const void* O = (const char*)ctx->ws_O.p + ((size_t)m * S + N) * E * ob;  // compact: one column per member
-    if (!fuse) RC(item_out_proj(ctx, L, O, X, Q, pm));
+    if (!fuse) RC(out_proj_ln(ctx, pm, true, L.item_out, O, X, Q));
     RC(mlp_sublayer(ctx, L, X, Q, pm, fuse ? O : nullptr));
   }
   return MMPFN_OK;
@@ -689,9 +652,6 @@ int run_forward_layers(mmpfn_ctx* ctx) {
   for (int l = 0; l < nl; ++l) RC(l == nl - 1 && !ctx->full_last ? last_layer_tail(ctx, l) : run_layer(ctx, l));
   return MMPFN_OK;
 }
-
-// workspace of the selected lane for a per-sublayer tap on a caller-provided state of S x T tokens
-int tap_workspace(mmpfn_ctx* ctx, int S, int T, int Npad) { return lane_workspace(ctx, S, T, Npad, 1, false); }
 
 // decoder over the test rows of M batched members (logits [M][Q][n_out]); the tile partials go
 // through the attention-output workspace, free once the last layer has run
@@ -1102,18 +1062,33 @@ int mmpfn_status(mmpfn_ctx* ctx) {
   return MMPFN_OK;
 }
 
-int mmpfn_item_attention(mmpfn_ctx* ctx, const void* q, const void* k, const void* vt, void* out, int S, int T, int H,
-                         int Npad, int s0, int nq, int nk, int kvh, int precision) {
+// The four item-attention taps' null and geometry check and their AttnLayerArgs: own-head rows [a0, a0 + na),
+// shared-KV rows [b0, b0 + nb) against head kvb, keys [0, nk).  Hmax: the heads the entry point's kernels take.  Every
+// entry point keeps its own precision rule.
+static int attn_tap_args(mmpfn_ctx* ctx, const void* q, const void* k, const void* vt, void* out, int S, int T, int H,
+                         int Hmax, int Npad, int nk, int a0, int na, int b0, int nb, int kvb, AttnLayerArgs& a) {
   if (!ctx || !q || !k || !vt || !out) return MMPFN_ERR_INVALID;
-  if (s0 < 0 || nq < 0 || s0 + nq > S || nk <= 0 || nk > Npad || Npad % 64 || H <= 0 || T <= 0 || kvh >= H)
+  if (a0 < 0 || na < 0 || a0 + na > S || b0 < 0 || nb < 0 || b0 + nb > S || nk <= 0 || nk > Npad || Npad % 64 ||
+      H <= 0 || H > Hmax || T <= 0 || kvb >= H)
     return fail(ctx, MMPFN_ERR_INVALID, "bad attention geometry");
   HIPCHK(hipSetDevice(ctx->device));
-  // this entry point runs the bf16 and the two fp32 element forms only (launch_attn_item); fp16 Q / K and the
-  // fp8 P.V variants go through mmpfn_item_attention_layer_ex
+  a = AttnLayerArgs{q, k, vt, out, S, T, H, Npad, nk};
+  a.a0 = a0, a.na = na, a.b0 = b0, a.nb = nb, a.kvb = kvb;
+  return MMPFN_OK;
+}
+
+int mmpfn_item_attention(mmpfn_ctx* ctx, const void* q, const void* k, const void* vt, void* out, int S, int T, int H,
+                         int Npad, int s0, int nq, int nk, int kvh, int precision) {
+  AttnLayerArgs a;
+  // kvh < 0: the rows against their own heads; else every head against K/V head kvh
+  if (kvh < 0) RC(attn_tap_args(ctx, q, k, vt, out, S, T, H, INT32_MAX, Npad, nk, s0, nq, 0, 0, -1, a));
+  else RC(attn_tap_args(ctx, q, k, vt, out, S, T, H, INT32_MAX, Npad, nk, 0, 0, s0, nq, kvh, a));
+  // this entry point runs the bf16 and the two fp32 element forms only; fp16 Q / K and the fp8 P.V variants go
+  // through mmpfn_item_attention_layer_ex
   if (precision != PREC_F32 && precision != PREC_BF16 && precision != PREC_F32_MFMA)
     return fail(ctx, MMPFN_ERR_INVALID, "bad precision (PREC_F32, PREC_BF16 or PREC_F32_MFMA; 16-bit / fp8 Q.K forms: "
                                         "mmpfn_item_attention_layer_ex)");
-  HIPCHK(launch_attn_item(q, k, vt, out, S, T, H, Npad, s0, nq, nk, kvh, precision, ctx->stream));
+  HIPCHK(launch_attn_layer(a, precision, ctx->stream));
   return MMPFN_OK;
 }
 
@@ -1215,29 +1190,21 @@ int mmpfn_kernel_timing_read(mmpfn_ctx* ctx, double* total_ms, int64_t* launches
 
 int mmpfn_item_attention_layer(mmpfn_ctx* ctx, const void* q, const void* k, const void* vt, void* out, int S, int T,
                                int H, int Npad, int N) {
-  if (!ctx || !q || !k || !vt || !out) return MMPFN_ERR_INVALID;
-  if (N <= 0 || N > S || N > Npad || Npad % 64 || H <= 0 || H > 8 || T <= 0)
-    return fail(ctx, MMPFN_ERR_INVALID, "bad attention geometry");
-  HIPCHK(hipSetDevice(ctx->device));
-  AttnLayerArgs a{q, k, vt, out, S, T, H, Npad, N};
-  a.a0 = 0, a.na = N, a.b0 = N, a.nb = S - N, a.kvb = 0;
-  HIPCHK(launch_attn_layer(a, ctx->stream));
+  AttnLayerArgs a;
+  RC(attn_tap_args(ctx, q, k, vt, out, S, T, H, 8, Npad, N, 0, N, N, S - N, 0, a));
+  HIPCHK(launch_attn_layer(a, PREC_BF16, ctx->stream));
   return MMPFN_OK;
 }
 
 int mmpfn_item_attention_layer_ex(mmpfn_ctx* ctx, const void* q, const void* k, const void* vt, void* out, int S,
                                   int T, int H, int Npad, int N, int precision) {
-  if (!ctx || !q || !k || !vt || !out) return MMPFN_ERR_INVALID;
-  if (N <= 0 || N > S || N > Npad || Npad % 64 || H <= 0 || H > 8 || T <= 0)
-    return fail(ctx, MMPFN_ERR_INVALID, "bad attention geometry");
+  AttnLayerArgs a;
+  RC(attn_tap_args(ctx, q, k, vt, out, S, T, H, 8, Npad, N, 0, N, N, S - N, 0, a));
   const bool qkb = (precision & MMPFN_ATTN_QK_BF16) != 0;  // the fp16 forward's form: bf16 q / k, fp16 out
   precision &= ~MMPFN_ATTN_QK_BF16;
   if (!prec_ok(precision)) return fail(ctx, MMPFN_ERR_INVALID, "bad precision");
   const PrecMode pm = decode_prec(precision, -1);  // the caller's operand types, whatever the table's width
   if (!pm.is16() || (qkb && !pm.f16())) return fail(ctx, MMPFN_ERR_INVALID, "bad precision");
-  HIPCHK(hipSetDevice(ctx->device));
-  AttnLayerArgs a{q, k, vt, out, S, T, H, Npad, N};
-  a.a0 = 0, a.na = N, a.b0 = N, a.nb = S - N, a.kvb = 0;
   if (pm.f8) {
     const int64_t n = (int64_t)T * H * 32 * Npad;
     RC(ensure(ctx, ctx->tap_v8, (size_t)n));
@@ -1245,20 +1212,18 @@ int mmpfn_item_attention_layer_ex(mmpfn_ctx* ctx, const void* q, const void* k, 
     a.vt8 = ctx->tap_v8.p, a.f8 = pm.f8;
   }
   a.qk_t = pm.f16() && !qkb ? DType::F16 : DType::BF16, a.o_t = pm.attn_out();
-  HIPCHK(launch_attn_layer(a, ctx->stream));
+  HIPCHK(launch_attn_layer(a, pm.base, ctx->stream));
   return MMPFN_OK;
 }
 
 int mmpfn_item_attention_cached(mmpfn_ctx* ctx, const void* q, const void* k0, const void* vt0, void* out, int S,
                                 int T, int H, int Npad, int N) {
-  if (!ctx || !q || !k0 || !vt0 || !out) return MMPFN_ERR_INVALID;
-  if (S <= 0 || N <= 0 || N > Npad || Npad % 64 || H <= 0 || H > 8 || T <= 0)
-    return fail(ctx, MMPFN_ERR_INVALID, "bad attention geometry");
-  HIPCHK(hipSetDevice(ctx->device));
-  AttnLayerArgs a{q, k0, vt0, out, S, T, H, Npad, N};
-  a.a0 = 0, a.na = 0, a.b0 = 0, a.nb = S, a.kvb = 0;  // every row against head 0 of the cache layout
+  AttnLayerArgs a;
+  // every row against head 0 of the cache layout
+  RC(attn_tap_args(ctx, q, k0, vt0, out, S, T, H, 8, Npad, N, 0, 0, 0, S, 0, a));
+  if (S <= 0) return fail(ctx, MMPFN_ERR_INVALID, "bad attention geometry");
   a.kv_bstride = (int64_t)Npad * 32;
-  HIPCHK(launch_attn_layer(a, ctx->stream));
+  HIPCHK(launch_attn_layer(a, PREC_BF16, ctx->stream));
   return MMPFN_OK;
 }
 
@@ -1275,7 +1240,7 @@ static int tap_check(mmpfn_ctx* ctx, int layer, const void* X, int precision) {
 int mmpfn_feature_attention(mmpfn_ctx* ctx, int layer, float* X, int S, int T, int precision) {
   RC(tap_check(ctx, layer, X, precision));
   if (S <= 0 || T <= 0) return fail(ctx, MMPFN_ERR_INVALID, "bad state geometry");
-  RC(tap_workspace(ctx, S, T, 64));
+  RC(lane_workspace(ctx, S, T, 64, 1, false));  // (a tap runs on the caller's state)
   const PrecMode pm = decode_prec(precision, T);
   return state_tap(ctx, X, (int64_t)S * T * ctx->d.emsize, pm, [&](void* Xs) {
     return feat_sublayer(ctx, ctx->w.layers[layer], Xs, S, T, 1, pm);
@@ -1286,7 +1251,7 @@ int mmpfn_item_attention_block(mmpfn_ctx* ctx, int layer, float* X, int S, int T
   RC(tap_check(ctx, layer, X, precision));
   if (S <= 0 || T <= 0 || N <= 0 || N > S) return fail(ctx, MMPFN_ERR_INVALID, "bad state geometry");
   const int Npad = (N + 63) / 64 * 64;
-  RC(tap_workspace(ctx, S, T, Npad));
+  RC(lane_workspace(ctx, S, T, Npad, 1, false));
   const PrecMode pm = decode_prec(precision, T);
   return state_tap(ctx, X, (int64_t)S * T * ctx->d.emsize, pm, [&](void* Xs) {
     return item_sublayer(ctx, layer, Xs, S, T, N, Npad, 1, pm, false);

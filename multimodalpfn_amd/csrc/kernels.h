@@ -110,22 +110,24 @@ hipError_t launch_mlp_rows(void* X, const void* W1perm, const void* W2perm, int6
                            hipStream_t st, const void* O = nullptr, const void* Wout = nullptr,
                            DType x_t = DType::F32);
 
+// one set of rows through one q|k|v (N = 576) or q (N = 192) weight [N][192], for the row-resident projections:
+// logical row m -> memory row (m / rdiv) * rmul + (m % rdiv) * rmul2 + roff of X; scattered to b = m / rdiv,
+// pos = roff + m % rdiv of Q [b][h][pos][32], K [b][h][pos][32] (Npad rows) and V^T [b][h][32][Npad]
+struct RowSet {
+  int64_t rdiv, rmul, rmul2, roff;
+  int M, N;
+  const void* W = nullptr;  // the launcher's operand form (launch_proj3_qkv: the hi plane of split_bf16)
+  int64_t w_lo = 0;         // launch_proj3_qkv: elements from W to its lo plane
+};
+
 // row-resident item-attention projections (bf16, K = 192, rowgemm.hip):
-//   QKV: X rows (remap (m/rdiv)*rmul + (m%rdiv)*rmul2 + roff) . W^T, W [N][192] (N = 576 or 192),
-//        scattered to Q [b][h][pos][32], K [b][h][pos][32] (Npad rows), V^T [b][h][32][Npad],
-//        b = m / rdiv, pos = roff + m % rdiv
+//   QKV: one or two row sets of X (train rows: q|k|v, test rows: q; W [N][192]) in ONE launch, the second set's blocks
+//        last; one set launches that set's blocks alone
 //   RES_LN: X <- LN(X + O . W^T), O [M][192] bf16, W [192][192] bf16
 //   x_t: the state's type, fp32 (bf16 W, Q / K; qk_t bf16) or fp16 (PREC_F16: X fp16, W fp16, Q / K in qk_t, fp16
 //   or bf16; V^T stays bf16); RES_LN: O bf16 / X fp32, or both fp16 with W rows in f16_row_perm order (weight_pack.h)
-hipError_t launch_rowgemm_qkv(const void* X, int64_t a_rdiv, int64_t a_rmul, int64_t a_rmul2, int64_t a_roff,
-                              const void* W, int M, int N, void* q, void* k, void* vt, int S, int Npad, int H,
-                              hipStream_t st, DType x_t = DType::F32, DType qk_t = DType::BF16);
-// two row sets (train rows: q|k|v, test rows: q) of the same token columns in ONE launch,
-// rows m -> memory row (m / rdiv) * a_rmul + m % rdiv + roff of each set
-hipError_t launch_rowgemm_qkv_pair(const void* X, int64_t rdiv1, int64_t roff1, const void* W1, int M1, int N1,
-                                   int64_t rdiv2, int64_t roff2, const void* W2, int M2, int N2, int64_t a_rmul,
-                                   void* q, void* k, void* vt, int S, int Npad, int H, hipStream_t st,
-                                   DType x_t = DType::F32, DType qk_t = DType::BF16);
+hipError_t launch_rowgemm_qkv(const void* X, const RowSet* sets, int nset, void* q, void* k, void* vt, int S, int Npad,
+                              int H, hipStream_t st, DType x_t = DType::F32, DType qk_t = DType::BF16);
 // C = (ln ? LayerNorm(A) : A) . W^T + bias: A fp32, bf16 or fp16 (a_t) [M][192], W [N][192] bf16, C bf16 [M][N], N % 64 == 0;
 // with CT: outputs [vt_from, N) transposed per group of Mk rows into CT [M / Mk][N - vt_from][Mk] (Mk % 32 == 0),
 // C then [M][vt_from]
@@ -137,17 +139,10 @@ hipError_t launch_rowgemm_resln(const void* O, const void* W, int64_t M, void* X
 
 // parity-mode (x3 split-bf16) row-resident projections of width 192 (rowgemm3.hip), fp32 in and out:
 // W = the hi plane [N][192] of split_bf16 (weight_pack.h), its lo plane at W + w_lo elements.
-//   QKV: up to two row sets in one launch (same remap / scatter as launch_rowgemm_qkv, fp32 Q / K / V^T)
+//   QKV: up to two row sets of X in one launch (fp32 Q / K / V^T)
 //   RES_LN: X <- LN(X + O . W^T), O fp32 [M][192]
-struct Proj3Set {
-  const float* A;
-  int64_t a_rdiv, a_rmul, a_rmul2, a_roff;
-  const void* W;
-  int64_t w_lo;
-  int M, N;  // N = 576 (q | k | v) or 192 (q)
-};
-hipError_t launch_proj3_qkv(const Proj3Set* sets, int nset, void* q, void* k, void* vt, int S, int Npad, int H,
-                            hipStream_t st);
+hipError_t launch_proj3_qkv(const float* X, const RowSet* sets, int nset, void* q, void* k, void* vt, int S, int Npad,
+                            int H, hipStream_t st);
 hipError_t launch_proj3_resln(const float* O, const void* W, int64_t w_lo, int64_t M, float* X, float eps,
                               hipStream_t st);
 
@@ -177,8 +172,48 @@ struct AttnArgs {
   int64_t o_bstride, o_qstride;
   int s0, nq, nk, kvh_fixed, H;
 };
+// one wave per block: PREC_BF16, PREC_F32 (split-bf16 products; the T <= 64 self-attention of the feature sublayer
+// takes its one-wave-per-(row, head) kernel) and PREC_F32_MFMA; four waves: PREC_F32_MFMA only
 hipError_t launch_attn(const AttnArgs& a, int batches, int prec, int waves_per_block, hipStream_t st);
-// task map + operands of the sample-axis attention kernels (attention.hip, attention_pipe.hip)
+
+// sample-axis (item) attention of one layer, the one entry to it (attention.hip):
+//   own-head rows [a0, a0+na) of every head against that head's K/V, and rows [b0, b0+nb) of
+//   every head against K/V head kvb (nb = 0: none); keys [0, nk), Npad % 64 == 0.
+//   kv_bstride > 0: K / V^T hold head 0 only, column blocks kv_bstride elements apart (train-KV
+//   cache; then na = 0 and kvb = 0)
+// base_prec (PrecMode::base) picks the kernel and the element type of q, k, vt and out:
+//   PREC_BF16, PREC_F16  the software-pipelined kernel in one launch (attention_pipe.hip, attn_pipe_kernel):
+//     f8 != 0: P.V and the row sums on block-scaled fp8 MFMA with vt8 = V^T in e4m3 (launch_vt_fp8), P in
+//     e4m3 (1) or e5m2 (2); vt (bf16) still serves the exact re-run path
+//     qk_t: Q and K bf16, or fp16 (S on the f16 MFMA; then o_t is fp16 too: the fp16 tap); o_t: O bf16 or fp16
+//     (PREC_F16's forward: bf16 Q / K, fp16 O); V^T stays bf16
+//   PREC_F32             attn_item3_kernel on fp32 Q / K / V^T (split bf16 three-product MFMAs), fp32 O, one launch;
+//     its cheap forms by set_x3_cheap_min_keys
+//   PREC_F32_MFMA        attn_item_kernel<0, 4> on fp32 operands: the own-head rows in one launch, the shared-KV rows
+//     in a second (a set of no rows: no launch)
+//   the prescale, fp8 and element-type fields apply to the 16-bit modes only
+struct AttnLayerArgs {
+  const void* q;
+  const void* k;
+  const void* vt;
+  void* out;
+  int S, T, H, Npad, nk;
+  int a0, na;                  // own-head query rows
+  int b0, nb, kvb;             // shared-KV query rows against kv head kvb
+  int64_t kv_bstride = 0;      // 0: no cache stride (K / V^T hold every head)
+  bool q_prescaled = false;    // Q already scaled by log2(e)/sqrt(32)
+  const void* vt8 = nullptr;
+  int f8 = 0;
+  DType qk_t = DType::BF16, o_t = DType::BF16;
+};
+constexpr int ATTN_ITEM_QPB = 256;  // queries per task of the 16-bit and PREC_F32 kernels' task maps
+hipError_t launch_attn_layer(const AttnLayerArgs& a, int base_prec, hipStream_t st);
+// bf16 -> e4m3 (saturating) of n elements (n % 8 == 0): the F8 attention's V^T operand
+hipError_t launch_vt_fp8(const void* vt, void* vt8, int64_t n, hipStream_t st);
+int set_x3_cheap_min_keys(int n, int form);  // previous value; mmpfn_set_parity_attention_min_keys
+
+// The seam between attention.hip (launch_attn_layer: the task map) and attention_pipe.hip (the pipelined kernel), and
+// nothing else's: task map + operands of the sample-axis attention kernels, by value
 struct Attn2Args {
   const __bf16* q;  // [B][H][S][32]
   const __bf16* k;  // [B][H][Npad][32]
@@ -197,43 +232,7 @@ struct Attn2Args {
   int qk_f16;          // q, k and o hold fp16 (S on f16 MFMA; the fp16 tap); vt stays bf16
   int o_f16;           // PREC_F16's forward: q, k bf16, o fp16 (every MFMA a bf16 one)
 };
-// software-pipelined bf16 sample-axis attention (attention_pipe.hip); tasks of ATTN_ITEM_QPB queries
-constexpr int ATTN_ITEM_QPB = 256;
 hipError_t launch_attn_pipe(const Attn2Args& a, hipStream_t st);
-// bf16 sample-axis attention of one layer in one launch (attention_pipe.hip, attn_pipe_kernel):
-//   own-head rows [a0, a0+na) of every head against that head's K/V, and rows [b0, b0+nb) of
-//   every head against K/V head kvb (nb = 0: none); keys [0, nk), Npad % 64 == 0.
-//   kv_bstride > 0: K / V^T hold head 0 only, column blocks kv_bstride elements apart (train-KV
-//   cache; then na = 0 and kvb = 0)
-//   f8 != 0: P.V and the row sums on block-scaled fp8 MFMA with vt8 = V^T in e4m3 (launch_vt_fp8), P in
-//   e4m3 (1) or e5m2 (2); vt (bf16) still serves the exact re-run path
-//   qk_t: Q and K bf16, or fp16 (S on the f16 MFMA; then o_t is fp16 too: the fp16 tap); o_t: O bf16 or fp16
-//   (PREC_F16's forward: bf16 Q / K, fp16 O); V^T stays bf16
-struct AttnLayerArgs {
-  const void* q;
-  const void* k;
-  const void* vt;
-  void* out;
-  int S, T, H, Npad, nk;
-  int a0, na;                  // own-head query rows
-  int b0, nb, kvb;             // shared-KV query rows against kv head kvb
-  int64_t kv_bstride = 0;      // 0: no cache stride (K / V^T hold every head)
-  bool q_prescaled = false;    // Q already scaled by log2(e)/sqrt(32)
-  const void* vt8 = nullptr;
-  int f8 = 0;
-  DType qk_t = DType::BF16, o_t = DType::BF16;
-};
-hipError_t launch_attn_layer(const AttnLayerArgs& a, hipStream_t st);
-// bf16 -> e4m3 (saturating) of n elements (n % 8 == 0): the F8 attention's V^T operand
-hipError_t launch_vt_fp8(const void* vt, void* vt8, int64_t n, hipStream_t st);
-// parity mode (PREC_F32) of launch_attn_layer on fp32 Q / K / V^T (split bf16 three-product MFMAs), fp32 O; the
-// prescale, fp8 and element-type fields do not apply
-int set_x3_cheap_min_keys(int n, int form);  // previous value; mmpfn_set_parity_attention_min_keys
-hipError_t launch_attn_item3(const AttnLayerArgs& a, hipStream_t st);
-// item attention: queries s in [s0, s0+nq), keys [0, nk); kv_head_fixed >= 0 forces that KV head
-hipError_t launch_attn_item(const void* q, const void* k, const void* vt, void* out, int S, int T, int H,
-                            int Npad, int s0, int nq, int nk, int kv_head_fixed, int prec, hipStream_t st,
-                            int64_t kv_bstride = 0);
 
 // ---- encoders / decoder ------------------------------------------------------------
 struct SlotParams {  // per (group, slot): how to transform raw column -> model input

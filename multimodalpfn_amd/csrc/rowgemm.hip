@@ -544,21 +544,20 @@ __global__ __launch_bounds__(256, 2) void rowgemm_resln_kernel(const RgArgs p) {
 
 namespace {
 // one row set of the QKV projection: args, row tiles per column and block count (0 blocks: M == 0)
-hipError_t qkv_rowset(const void* X, int64_t a_rdiv, int64_t a_rmul, int64_t a_rmul2, int64_t a_roff, const void* W,
-                      int M, int N, void* q, void* k, void* vt, int S, int Npad, int H, RgArgs& a, int& tiles,
-                      int64_t& nblk) {
+hipError_t qkv_rowset(const void* X, const RowSet& s, void* q, void* k, void* vt, int S, int Npad, int H, RgArgs& a,
+                      int& tiles, int64_t& nblk) {
   a = RgArgs{};
   tiles = 1, nblk = 0;
-  if (M <= 0) return hipSuccess;
-  if ((N != GE && N != 3 * GE) || H * 32 != GE) return hipErrorInvalidValue;
-  a.A = X, a.a_rdiv = a_rdiv, a.a_rmul = a_rmul, a.a_rmul2 = a_rmul2, a.a_roff = a_roff;
-  a.W = W, a.M = M, a.N = N;
+  if (s.M <= 0) return hipSuccess;
+  if ((s.N != GE && s.N != 3 * GE) || H * 32 != GE) return hipErrorInvalidValue;
+  a.A = X, a.a_rdiv = s.rdiv, a.a_rmul = s.rmul, a.a_rmul2 = s.rmul2, a.a_roff = s.roff;
+  a.W = s.W, a.M = s.M, a.N = s.N;
   a.q = q, a.k = k, a.vt = (bf16*)vt, a.S = S, a.Npad = Npad, a.H = H;
-  // blocks tile each column b separately: nb = M / a_rdiv columns of a_rdiv rows
-  if (a_rdiv <= 0 || M % a_rdiv != 0) return hipErrorInvalidValue;
-  if (N == 3 * GE && (a_roff % 8 != 0 || a_roff + a_rdiv > Npad)) return hipErrorInvalidValue;  // 16-B V^T stores
-  tiles = (int)((a_rdiv + GROWS - 1) / GROWS);
-  nblk = (int64_t)tiles * (M / a_rdiv);
+  // blocks tile each column b separately: nb = M / rdiv columns of rdiv rows
+  if (s.rdiv <= 0 || s.M % s.rdiv != 0) return hipErrorInvalidValue;
+  if (s.N == 3 * GE && (s.roff % 8 != 0 || s.roff + s.rdiv > Npad)) return hipErrorInvalidValue;  // 16-B V^T stores
+  tiles = (int)((s.rdiv + GROWS - 1) / GROWS);
+  nblk = (int64_t)tiles * (s.M / s.rdiv);
   return hipSuccess;
 }
 // fp32 state: bf16 Q / K; fp16 state: fp16 or bf16 Q / K
@@ -567,38 +566,23 @@ bool qkv_types_ok(DType x_t, DType qk_t) {
 }
 }  // namespace
 
-hipError_t launch_rowgemm_qkv(const void* X, int64_t a_rdiv, int64_t a_rmul, int64_t a_rmul2, int64_t a_roff,
-                              const void* W, int M, int N, void* q, void* k, void* vt, int S, int Npad, int H,
-                              hipStream_t st, DType x_t, DType qk_t) {
-  RgArgs a;
-  int tiles;
-  int64_t nblk;
-  if (!qkv_types_ok(x_t, qk_t)) return hipErrorInvalidValue;
-  const bool f16 = x_t == DType::F16, qk_bf16 = qk_t == DType::BF16;
-  hipError_t e = qkv_rowset(X, a_rdiv, a_rmul, a_rmul2, a_roff, W, M, N, q, k, vt, S, Npad, H, a, tiles, nblk);
-  if (e != hipSuccess || nblk == 0) return e;
-  const dim3 g((unsigned)nblk);
-  if (f16 && qk_bf16) hipLaunchKernelGGL((rowgemm_qkv2_kernel<true, true>), g, dim3(256), 0, st, a, tiles, a, tiles, (int)nblk);
-  else if (f16) hipLaunchKernelGGL((rowgemm_qkv2_kernel<true, false>), g, dim3(256), 0, st, a, tiles, a, tiles, (int)nblk);
-  else hipLaunchKernelGGL((rowgemm_qkv2_kernel<false, false>), g, dim3(256), 0, st, a, tiles, a, tiles, (int)nblk);
-  return hipGetLastError();
-}
-
-hipError_t launch_rowgemm_qkv_pair(const void* X, int64_t rdiv1, int64_t roff1, const void* W1, int M1, int N1,
-                                   int64_t rdiv2, int64_t roff2, const void* W2, int M2, int N2, int64_t a_rmul,
-                                   void* q, void* k, void* vt, int S, int Npad, int H, hipStream_t st, DType x_t,
-                                   DType qk_t) {
+hipError_t launch_rowgemm_qkv(const void* X, const RowSet* sets, int nset, void* q, void* k, void* vt, int S, int Npad,
+                              int H, hipStream_t st, DType x_t, DType qk_t) {
   RgArgs a1, a2;
   int t1, t2;
-  int64_t n1, n2;
-  if (!qkv_types_ok(x_t, qk_t)) return hipErrorInvalidValue;
+  int64_t n1, n2 = 0;
+  if (nset < 1 || nset > 2 || !qkv_types_ok(x_t, qk_t)) return hipErrorInvalidValue;
   const bool f16 = x_t == DType::F16, qk_bf16 = qk_t == DType::BF16;
-  hipError_t e = qkv_rowset(X, rdiv1, a_rmul, 1, roff1, W1, M1, N1, q, k, vt, S, Npad, H, a1, t1, n1);
+  hipError_t e = qkv_rowset(X, sets[0], q, k, vt, S, Npad, H, a1, t1, n1);
   if (e != hipSuccess) return e;
-  e = qkv_rowset(X, rdiv2, a_rmul, 1, roff2, W2, M2, N2, q, k, vt, S, Npad, H, a2, t2, n2);
-  if (e != hipSuccess) return e;
+  if (nset == 2) {
+    e = qkv_rowset(X, sets[1], q, k, vt, S, Npad, H, a2, t2, n2);
+    if (e != hipSuccess) return e;
+    if (n1 == 0) a1 = a2, t1 = t2;  // blocks index the second set only
+  } else {
+    a2 = a1, t2 = t1;  // the one set twice: every block is below n1
+  }
   if (n1 + n2 == 0) return hipSuccess;
-  if (n1 == 0) a1 = a2, t1 = t2;  // blocks index the second set only
   const dim3 g((unsigned)(n1 + n2));
   if (f16 && qk_bf16) hipLaunchKernelGGL((rowgemm_qkv2_kernel<true, true>), g, dim3(256), 0, st, a1, t1, a2, t2, (int)n1);
   else if (f16) hipLaunchKernelGGL((rowgemm_qkv2_kernel<true, false>), g, dim3(256), 0, st, a1, t1, a2, t2, (int)n1);

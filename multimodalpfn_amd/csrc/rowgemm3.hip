@@ -276,13 +276,13 @@ hipError_t launch_p3(const P3Args& a, hipStream_t st) {
   return hipGetLastError();
 }
 
-bool fill_set(const Proj3Set& s, P3Set& o) {
-  if (s.M < 0 || (s.M > 0 && (!s.A || !s.W || s.w_lo <= 0 || s.a_rdiv <= 0))) return false;
+bool fill_set(const float* A, const RowSet& s, P3Set& o) {
+  if (s.M < 0 || (s.M > 0 && (!A || !s.W || s.w_lo <= 0 || s.rdiv <= 0))) return false;
   if (s.N != P3E && s.N != 3 * P3E) return false;
-  if (s.a_rdiv > INT32_MAX || s.a_rmul > INT32_MAX || s.a_rmul2 > INT32_MAX || s.a_roff > INT32_MAX || s.a_rmul < 0 ||
-      s.a_rmul2 < 0 || s.a_roff < 0)
+  if (s.rdiv > INT32_MAX || s.rmul > INT32_MAX || s.rmul2 > INT32_MAX || s.roff > INT32_MAX || s.rmul < 0 ||
+      s.rmul2 < 0 || s.roff < 0)
     return false;
-  o.A = s.A, o.a_rdiv = (int)s.a_rdiv, o.a_rmul = (int)s.a_rmul, o.a_rmul2 = (int)s.a_rmul2, o.a_roff = (int)s.a_roff;
+  o.A = A, o.a_rdiv = (int)s.rdiv, o.a_rmul = (int)s.rmul, o.a_rmul2 = (int)s.rmul2, o.a_roff = (int)s.roff;
   o.W = (const bf16*)s.W, o.w_lo = s.w_lo, o.M = s.M, o.npanel = s.N / P3E;
   o.tiles = (s.M + P3TILE - 1) / P3TILE;
   return true;
@@ -290,14 +290,14 @@ bool fill_set(const Proj3Set& s, P3Set& o) {
 
 }  // namespace
 
-hipError_t launch_proj3_qkv(const Proj3Set* sets, int nset, void* q, void* k, void* vt, int S, int Npad, int H,
-                            hipStream_t st) {
+hipError_t launch_proj3_qkv(const float* X, const RowSet* sets, int nset, void* q, void* k, void* vt, int S, int Npad,
+                            int H, hipStream_t st) {
   if (nset < 1 || nset > 2 || H * 32 != P3E) return hipErrorInvalidValue;
   P3Args a{};
   a.nset = nset, a.q = (float*)q, a.k = (float*)k, a.vt = (float*)vt, a.S = S, a.Npad = Npad, a.H = H;
   int64_t total = 0;
   for (int i = 0; i < nset; ++i) {
-    if (!fill_set(sets[i], a.set[i])) return hipErrorInvalidValue;
+    if (!fill_set(X, sets[i], a.set[i])) return hipErrorInvalidValue;
     if (a.set[i].npanel == 3 && sets[i].M > 0 && (!k || !vt)) return hipErrorInvalidValue;
     total += (int64_t)a.set[i].npanel * a.set[i].tiles;
   }
@@ -312,8 +312,8 @@ hipError_t launch_proj3_resln(const float* O, const void* W, int64_t w_lo, int64
   if (M <= 0) return hipSuccess;
   if (M > INT32_MAX - P3TILE || !O || !W || !X || w_lo <= 0) return hipErrorInvalidValue;
   P3Args a{};
-  Proj3Set s{O, 1, 1, 0, 0, W, w_lo, (int)M, P3E};
-  if (!fill_set(s, a.set[0])) return hipErrorInvalidValue;
+  const RowSet s{1, 1, 0, 0, (int)M, P3E, W, w_lo};
+  if (!fill_set(O, s, a.set[0])) return hipErrorInvalidValue;
   a.nset = 1, a.total = a.set[0].tiles, a.X = X, a.eps = eps;
   return launch_p3<true>(a, st);
 }

@@ -2,8 +2,9 @@
 an .npz, so that two builds meant to be bitwise equal can be compared:  MMPFN_LIB=... python tools/lib_outputs.py out.npz
 then  python tools/lib_outputs.py --compare a.npz b.npz
 Legs: the fp16, bf16, fp32 (split-bf16) and fp32-MFMA logits of every golden case; the two fp16 + fp8 P.V modes on
-pad_ufes_12l; forward_many with 2 lanes and batch 2 on one golden; and a table wider than 64 tokens per row (the bf16
-fallback path: the bf16 and fp32 forwards, the cached predict, and the layer-0 attention taps)."""
+pad_ufes_12l, and its four base modes with the last layer run in full; forward_many with 2 lanes and batch 2 on one
+golden; a table wider than 64 tokens per row (the bf16 fallback path) in the bf16, fp32 and fp32-MFMA modes: the
+forward, the cached predict, and the layer-0 attention taps; and the four C-ABI item-attention taps on a seeded case."""
 import sys
 from pathlib import Path
 
@@ -66,16 +67,50 @@ def wide_legs(_lib):
     y = synth_labels(S, 3, 21)[:N]
     res = {}
     with torch.inference_mode():
-        res["wide_bf16"] = eng.forward(x, None, y, _lib.PREC_BF16)
-        res["wide_f32"] = eng.forward(x, None, y, _lib.PREC_F32)
-        cache = eng.cache_build(x[:N], None, y, _lib.PREC_BF16)
-        res["wide_cached_bf16"] = eng.cache_predict(cache, x[N:], None)
-        cache.free()
         X = eng.embed_state(x, None, y, _lib.PREC_F32)
-        res["wide_feat_tap_bf16"] = eng.feature_attention(0, X, _lib.PREC_BF16)
-        res["wide_item_tap_bf16"] = eng.item_attention_block(0, X, N, _lib.PREC_BF16)
+        for name, p in (("bf16", _lib.PREC_BF16), ("f32", _lib.PREC_F32), ("f32mfma", _lib.PREC_F32_MFMA)):
+            res[f"wide_{name}"] = eng.forward(x, None, y, p)
+            cache = eng.cache_build(x[:N], None, y, p)
+            res[f"wide_cached_{name}"] = eng.cache_predict(cache, x[N:], None)
+            cache.free()
+            res[f"wide_feat_tap_{name}"] = eng.feature_attention(0, X, p)
+            res[f"wide_item_tap_{name}"] = eng.item_attention_block(0, X, N, p)
         eng.status()
     return {k: v.cpu().numpy() for k, v in res.items()}
+
+
+def attention_tap_legs(_lib):
+    """The four C-ABI item-attention taps, S = 100, N = 70 (Npad = 128), T = 2, H = 6: mmpfn_item_attention in its
+    three codes (train rows on their own heads, kvh = -1, then test rows against head 0), the bf16 layer tap, the
+    layer_ex tap (fp8 P.V, fp16, and the fp16 forward's form) and the cached tap."""
+    import torch
+    from test_parity_gpu import _launch_cached, _launch_layer, _qkv_case
+
+    S, N, T, H, d = 100, 70, 2, 6, 32
+    q, k, v, Npad = _qkv_case(S, N, T, H, d, seed=5)
+    kp = torch.zeros(T, H, Npad, d)
+    kp[:, :, :N] = k
+    vt = torch.zeros(T, H, d, Npad)
+    vt[:, :, :, :N] = v.transpose(-1, -2)
+    lib = _lib.load_library()
+    ctx = lib.mmpfn_create(0, None)
+    res = {}
+    for code in (_lib.PREC_F32, _lib.PREC_BF16, _lib.PREC_F32_MFMA):
+        dt = torch.bfloat16 if code == _lib.PREC_BF16 else torch.float32
+        qd, kd, vd = q.to("cuda", dt), kp.to("cuda", dt), vt.to("cuda", dt)
+        out = torch.zeros(T, S, H * d, device="cuda", dtype=dt)
+        for s0, nq, kvh in ((0, N, -1), (N, S - N, 0)):
+            rc = lib.mmpfn_item_attention(ctx, qd.data_ptr(), kd.data_ptr(), vd.data_ptr(), out.data_ptr(), S, T, H,
+                                          Npad, s0, nq, N, kvh, code)
+            assert rc == 0, (code, kvh, rc)
+        torch.cuda.synchronize()
+        res[f"tap_item_attention_{code}"] = out.float().cpu()
+    lib.mmpfn_destroy(ctx)
+    res["tap_layer"] = _launch_layer(q, k, v, Npad, N, 1)
+    for code in (_lib.PREC_BF16_F8, _lib.PREC_F16, _lib.PREC_F16 | _lib.ATTN_QK_BF16):
+        res[f"tap_layer_ex_{code}"] = _launch_layer(q, k, v, Npad, N, code)
+    res["tap_cached"] = _launch_cached(q, k[:, 0], v[:, 0], Npad, N)
+    return {k: v.numpy() for k, v in res.items()}
 
 
 def main():
@@ -97,7 +132,12 @@ def main():
             for name, p in (("f16_f8", _lib.PREC_F16_F8), ("f16_f8e5", _lib.PREC_F16_F8E5)):
                 res[f"{case}_{name}"] = run_case(z, model, precision=p)
             res[f"{case}_lanes2_batch2_bf16"] = lanes_leg(z, model, _lib)
+            model.engine().full_last_layer = True  # (the default, pruned form: the legs above)
+            for name, p in modes:
+                res[f"{case}_full_last_{name}"] = run_case(z, model, precision=p)
+            model.engine().full_last_layer = False
     res.update(wide_legs(_lib))
+    res.update(attention_tap_legs(_lib))
     np.savez(sys.argv[1], **res)
     print("saved", len(res), "outputs to", sys.argv[1])
 
