@@ -28,6 +28,9 @@
  *   mmpfn_item_attention_cached
  *       <- model/layer.py:344-358 with multi_head_attention.py:461-472: test rows of
  *          every head against the cached head-0 K/V of the train rows (fit_with_cache)
+ *   mmpfn_bar_head
+ *       <- regressor.py:652-706 (temperature, cancel mask, translate_probs_across_borders, ensemble mean) and
+ *          :732-765 _logits_to_output on the renormalised FullSupportBarDistribution
  *   mmpfn_status
  *       <- model/transformer.py:727-731,790-796 NaN checks (ValueError)
  *   mmpfn_feature_attention / mmpfn_item_attention_block / mmpfn_mlp_ln
@@ -72,6 +75,11 @@ extern "C" {
 #define MMPFN_MIXER_MGM_CAP 2
 #define MMPFN_MIXER_MOE 3
 
+#define MMPFN_TARGET_CLASS 0 /* class codes sum(y > uniq) (MulticlassClassificationTargetEncoder, encoders.py:949-974) */
+#define MMPFN_TARGET_VALUE 1 /* the target itself, as the caller standardised it (a regression model: no class-code
+                                step; uniq / U of the forward entry points are ignored and may be NULL / 0; the
+                                y encoder's Linear is y_encoder.1.layer.*, the decoder n_out = the criterion's bars wide) */
+
 typedef struct mmpfn_ctx mmpfn_ctx;
 
 typedef struct mmpfn_model_desc {
@@ -89,6 +97,7 @@ typedef struct mmpfn_model_desc {
   int remove_duplicate_features; /* encoder Linear step index 6 instead of 5 */
   float ln_eps;           /* 1e-5 */
   float outlier_sigma;    /* 12 for classification; <= 0 disables soft clipping */
+  int target_kind;        /* MMPFN_TARGET_*: what the label token embeds (the y encoder of loading.py:374-398) */
 } mmpfn_model_desc;
 
 /* ---- lifecycle ------------------------------------------------------------------ */
@@ -103,7 +112,7 @@ const char* mmpfn_version(void);
  * refused here with MMPFN_ERR_INVALID (mmpfn_last_error names the field), never by a launch in a forward:
  *   emsize 192 in 6 heads of 32; nhid a multiple of 192, and with a mixer a multiple of 384 (nhid / 2, the
  *   modality heads' down-projection depth, must be a multiple of 64: nhid 192 and 576 are refused);
- *   nlayers, n_out >= 1; 1 <= features_per_group <= encoder_features <= 8;
+ *   nlayers, n_out >= 1; target_kind one of MMPFN_TARGET_*; 1 <= features_per_group <= encoder_features <= 8;
  *   MGM+CAP: cap_heads a divisor of 192 other than 1 (head dims 96 .. 1 have a CAP attention kernel, head dim 192
  *   has none: cap_heads 1 is refused). */
 int mmpfn_set_model(mmpfn_ctx* ctx, const mmpfn_model_desc* desc);
@@ -118,7 +127,8 @@ int mmpfn_mixer_forward(mmpfn_ctx* ctx, const float* image, int S, int n_mod, fl
 /* ---- one ensemble member's forward ------------------------------------------------
  * x        [S][F] fp32 (NULL when tabular input is absent)
  * tokens   [S][C][E] mixer tokens (NULL / C = 0 when there is no image)
- * y_train  [N] fp32 class codes; uniq [U] sorted unique train codes (after NaN fill)
+ * y_train  [N] fp32 class codes; uniq [U] sorted unique train codes (after NaN fill) -- MMPFN_TARGET_VALUE: the
+ *          standardised targets, uniq / U unused
  * pos_rand [G + C][E/4]: torch.randn from the model's CPU generator
  *          (transformer.py:421-424,925-931), G = ceil(F / features_per_group)
  * logits   [S - N][n_out] fp32 output                                               */
@@ -153,6 +163,30 @@ int mmpfn_state_tokens(const mmpfn_ctx* ctx); /* T of the current state */
  * C = n_cls when sliced or permuted, else n_out. */
 int mmpfn_aggregate(mmpfn_ctx* ctx, const float* logits, int M, int Q, int n_out, const int* perms, int n_cls,
                     float temperature, int average_before_softmax, const float* class_weights, float* probs);
+
+/* Bar-distribution head of the regression ensemble (regressor.py:691-706, utils.py:659-700; then the renormalised
+ * criterion's mean / mode / icdf, bar_distribution.py:239-332,588-597), always fp32, one pass over the logits:
+ * logits [M][Q][B]; cancel [M][ldc] bytes (ldc >= B), non-zero = the bar's logit is -inf for that member (NULL: no
+ *   member cancels);
+ * idx / share [M][ldt] (ldt >= B + 1): per member and target border j, the member's bucket that holds the border and the
+ *   border's share of it as utils.py:662-670 computes them (in float32, on the host: they depend on the borders
+ *   only); idx -1 / -2: the member's CDF at that border is 0 / 1 whatever the row (utils.py:675-676,697-698).
+ *   Dense rows (ldt = B + 1, ldc = B) are fine; rows padded to a multiple of 4 entries on 16-byte-aligned bases are
+ *   read in 16-byte (tables) and 4-byte (mask) pieces, which is what HipEngine.bar_head uploads;
+ * inv_temperature = 1 / softmax_temperature; average_before_softmax 0/1 (regressor.py:700-703);
+ * of the renormalised criterion (regressor.py:516-518): borders [B + 1], bucket_means [B] with the two half-normal
+ *   end means (bar_distribution.py:588-597), mode_means [B] the plain ones and widths [B] (:328-332);
+ * levels [K] quantile levels (the median is the level 0.5).
+ * Outputs: out_logits [Q][B] the ensemble's log-probabilities (NULL: not stored); mean [Q], mode [Q],
+ * quantiles [K][Q] of softmax(out_logits), as the reference's criterion applies it again.
+ * B <= MMPFN_BAR_MAX_BARS, M <= MMPFN_BAR_MAX_MEMBERS, K <= MMPFN_BAR_MAX_LEVELS, else MMPFN_ERR_INVALID. */
+#define MMPFN_BAR_MAX_BARS 8192
+#define MMPFN_BAR_MAX_MEMBERS 1024
+#define MMPFN_BAR_MAX_LEVELS 64
+int mmpfn_bar_head(mmpfn_ctx* ctx, const float* logits, int M, int Q, int B, const unsigned char* cancel, int ldc,
+                   const int* idx, const float* share, int ldt, float inv_temperature, int average_before_softmax,
+                   const float* borders, const float* bucket_means, const float* mode_means, const float* widths,
+                   const float* levels, int K, float* out_logits, float* mean, float* mode, float* quantiles);
 
 /* Synchronises the context stream and reports deferred device-side errors
  * (MMPFN_ERR_NAN when the embedded input held NaNs). */

@@ -20,6 +20,7 @@ MMPFN_ERR_HIP = -2
 MMPFN_ERR_NAN = -3
 MMPFN_ERR_STATE = -4
 MMPFN_ERR_WEIGHT = -5
+BAR_MAX_BARS, BAR_MAX_MEMBERS, BAR_MAX_LEVELS = 8192, 1024, 64  # mmpfn_bar_head's limits (MMPFN_BAR_MAX_*)
 
 PREC_F32 = 0       # parity mode: split-bf16 three-product MFMAs (fp32 operands to 2^-16), fp32 softmax / LN
 PREC_BF16 = 1      # 16-bit mode with bf16 operands on an fp32 state (MMPFN_AUTOCAST=bf16)
@@ -63,6 +64,7 @@ def autocast_precision() -> int:
     and faster -- unless ``MMPFN_AUTOCAST=bf16`` selects PREC_BF16."""
     return PREC_BF16 if os.environ.get("MMPFN_AUTOCAST", "f16").lower() == "bf16" else PREC_F16
 
+TARGET_CLASS, TARGET_VALUE = 0, 1  # mmpfn_model_desc.target_kind (MMPFN_TARGET_*)
 MIXER_NONE, MIXER_MGM, MIXER_MGM_CAP, MIXER_MOE = 0, 1, 2, 3
 MIXER_CODES = {"MGM": MIXER_MGM, "MGM+CAP": MIXER_MGM_CAP, "MoE": MIXER_MOE, None: MIXER_NONE}
 
@@ -83,6 +85,7 @@ class ModelDesc(ctypes.Structure):
         ("remove_duplicate_features", ctypes.c_int),
         ("ln_eps", ctypes.c_float),
         ("outlier_sigma", ctypes.c_float),
+        ("target_kind", ctypes.c_int),
     ]
 
 
@@ -128,6 +131,8 @@ SIGNATURES = [
     ("mmpfn_siphash24_rows", _i, [_vp, _i64, _i64, _vp]),
     ("mmpfn_set_parity_attention_min_keys", _i, [_i, _i]),
     ("mmpfn_set_full_last_layer", _i, [_vp, _i]),
+    ("mmpfn_bar_head", _i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp,
+                            _vp, _vp]),
 ]
 
 # include/mmpfn_modality.h (modality encoders: DINOv2 ViT, ELECTRA text tower)

@@ -26,12 +26,15 @@ def initialize_mmpfn_model(
     cap_heads: int,
     features_per_group: int,
 ):
-    """Load the checkpoint -> (model, config, None) for the classifier (``base.py:54-120``)."""
+    """Load the checkpoint -> (model, config, None) for the classifier, (model, config, bar distribution) for
+    the regressor (``base.py:54-120``)."""
     if isinstance(model_path, str) and model_path == "auto":
         model_path = None  # type: ignore[assignment]
-    model, _, config = load_model_criterion_config(
+    if which not in ("classifier", "regressor"):
+        raise ValueError(f"Invalid which: {which}")
+    model, criterion, config = load_model_criterion_config(
         model_path=model_path,
-        check_bar_distribution_criterion=False,
+        check_bar_distribution_criterion=which == "regressor",
         cache_trainset_representation=(fit_mode == "fit_with_cache"),
         which=which,
         version="v2",
@@ -42,7 +45,7 @@ def initialize_mmpfn_model(
         cap_heads=cap_heads,
         features_per_group=features_per_group,
     )
-    return model, config, None
+    return model, config, criterion if which == "regressor" else None
 
 
 def determine_precision(inference_precision, device_: torch.device) -> tuple[bool, torch.dtype | None, int]:

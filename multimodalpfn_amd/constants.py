@@ -76,3 +76,6 @@ DEFAULT_NUMPY_PREPROCESSING_DTYPE = np.float64
 ENSEMBLE_CONFIGURATION_MAX_STEP = 2
 MAXIMUM_FEATURE_SHIFT = 1_000
 CLASS_SHUFFLE_OVERESTIMATE_FACTOR = 3
+# a transformed border beyond these counts as broken, like a non-finite one (constants.py:216-217)
+REGRESSION_NAN_BORDER_LIMIT_UPPER = 1e3
+REGRESSION_NAN_BORDER_LIMIT_LOWER = -1e3

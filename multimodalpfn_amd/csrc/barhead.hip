@@ -1,0 +1,371 @@
+// Bar-distribution head of the regression ensemble (regressor.py:691-706 with utils.py:659-700, then the
+// renormalised criterion's mean / mode / icdf, bar_distribution.py:239-332,588-597): M members' logits over B bars
+// -> one predictive distribution per test row and its point estimates, in one pass over the logits.  Always fp32.
+#include "common.h"
+#include "kernels.h"
+
+namespace mmpfn {
+namespace {
+
+constexpr int kBarThreads = 256;  // 4 waves
+
+// Block-wide helpers on `red` (4 floats).  The leading barrier frees `red` from the previous use.
+__device__ __forceinline__ float bar_block_max(float v, float* red) {
+  v = wave_max(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+__device__ __forceinline__ float bar_block_sum(float v, float* red) {
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+__device__ __forceinline__ float wave_inclusive_scan(float x, int lane) {
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const float y = __shfl_up(x, d, 64);
+    if (lane >= d) x += y;
+  }
+  return x;
+}
+
+// A thread's bars: NV groups of 4 consecutive bars; wave w owns bars [w * 256 NV, (w + 1) * 256 NV), group i of lane l
+// starts at bar w * 256 NV + 256 i + 4 l, so a wave instruction covers 256 consecutive bars (1 KiB).
+template <int NV>
+__device__ __forceinline__ int bar_index(int i) {
+  return (threadIdx.x >> 6) * (256 * NV) + 256 * i + 4 * (threadIdx.x & 63);
+}
+
+// Exclusive prefix sums of the block's values e (>= 0, zero beyond B) in bar order, and their total.  Lane-local
+// sums of 4, a wave scan per group with a running carry, then the lower waves' totals.
+template <int NV>
+__device__ __forceinline__ float bar_block_scan(const float (&e)[NV][4], float (&c)[NV][4], float* red) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float carry = 0.f;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const float t = (e[i][0] + e[i][1]) + (e[i][2] + e[i][3]);
+    const float inc = wave_inclusive_scan(t, lane);
+    float ex = __shfl_up(inc, 1, 64);
+    if (lane == 0) ex = 0.f;
+    float base = carry + ex;
+    c[i][0] = base;
+    base += e[i][0];
+    c[i][1] = base;
+    base += e[i][1];
+    c[i][2] = base;
+    base += e[i][2];
+    c[i][3] = base;
+    carry += __shfl(inc, 63, 64);
+  }
+  __syncthreads();
+  if (lane == 0) red[wave] = carry;
+  __syncthreads();
+  const float t0 = red[0], t1 = red[1], t2 = red[2], t3 = red[3];
+  const float off = wave == 0 ? 0.f : wave == 1 ? t0 : wave == 2 ? t0 + t1 : (t0 + t1) + t2;
+#pragma unroll
+  for (int i = 0; i < NV; ++i)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) c[i][k] += off;
+  return ((t0 + t1) + t2) + t3;
+}
+
+struct BarHeadArgs {
+  const float* logits;          // [M][Q][B]
+  const unsigned char* cancel;  // [M][ldc] or null
+  const int* idx;               // [M][ldt]: source bucket, -1: CDF forced to 0, -2: forced to 1
+  const float* share;           // [M][ldt]
+  const float* borders;         // [B + 1] renormalised criterion
+  const float* means;           // [B] bucket means with the half-normal ends
+  const float* mode_means;      // [B] plain bucket means
+  const float* widths;          // [B]
+  const float* levels;          // [K]
+  float* out_logits;            // [Q][B] or null
+  float* mean;                  // [Q]
+  float* mode;                  // [Q]
+  float* quantiles;             // [K][Q]
+  int M, Q, B, K;
+  float inv_temp;
+  int avg_before;
+  int ldt, ldc;      // row strides of the tables (>= B + 1) and of the cancel mask (>= B)
+  int tvec, cvec;    // the strides and bases allow 16-byte table loads / 4-byte mask loads (padded rows)
+};
+
+template <int NV>
+__global__ __launch_bounds__(kBarThreads) void bar_head_kernel(const BarHeadArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float bar_lds[];
+  __shared__ float red[4];
+  __shared__ int red_i[4];
+  const int B = a.B, q = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int ldp = (B + 3) & ~3;
+  float* const p_s = bar_lds;        // [ldp] a member's bucket probabilities, then the final ones
+  float* const c_s = bar_lds + ldp;  // [ldp] their exclusive prefix sums, then the final inclusive ones
+
+  float acc[NV][4];
+#pragma unroll
+  for (int i = 0; i < NV; ++i)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) acc[i][k] = 0.f;
+
+  // a member's row as its softmax reads it, before the temperature: cancelled bars and the padding beyond B at -inf
+  auto load_row = [&](int m, float (&v)[NV][4]) {
+    const float* row = a.logits + ((int64_t)m * a.Q + q) * B;
+    const unsigned char* cm = a.cancel ? a.cancel + (int64_t)m * a.ldc : nullptr;
+    const bool vec = (reinterpret_cast<uintptr_t>(row) & 15) == 0;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int j0 = bar_index<NV>(i);
+      if (vec && j0 + 3 < B) {
+        const f32x4 r = *reinterpret_cast<const f32x4*>(row + j0);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[i][k] = r[k];
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[i][k] = j0 + k < B ? row[j0 + k] : -INFINITY;
+      }
+      if (cm && j0 < B) {
+        if (a.cvec) {  // the group's four mask bytes in one load (a padded row: ldc >= B rounded up to 4)
+          const uint32_t w = *reinterpret_cast<const uint32_t*>(cm + j0);
+#pragma unroll
+          for (int k = 0; k < 4; ++k)
+            if (j0 + k < B && ((w >> (8 * k)) & 0xffu)) v[i][k] = -INFINITY;
+        } else {
+#pragma unroll
+          for (int k = 0; k < 4; ++k)
+            if (j0 + k < B && cm[j0 + k]) v[i][k] = -INFINITY;
+        }
+      }
+    }
+  };
+
+  // The members one after the other.  What a member reads from global memory is asked for a phase ahead of its
+  // use -- the next member's row while this one's softmax runs, this member's border tables before its softmax --
+  // since a block's phases are serial and only two or three blocks share a CU.
+  float nxt[NV][4];
+  load_row(0, nxt);
+  for (int m = 0; m < a.M; ++m) {
+    float e[NV][4], c[NV][4];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        e[i][k] = nxt[i][k] * a.inv_temp;  // (-inf stays -inf: inv_temp > 0)
+        mx = fmaxf(mx, e[i][k]);
+      }
+    if (m + 1 < a.M) load_row(m + 1, nxt);
+    const int* ix = a.idx + (int64_t)m * a.ldt;
+    const float* sh = a.share + (int64_t)m * a.ldt;
+    int tix[NV][4];  // the tables at the thread's own borders; beyond the last border the CDF is 1
+    float tsh[NV][4];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int j0 = bar_index<NV>(i);
+      if (a.tvec && j0 <= B) {  // 16-byte pieces of a padded row (ldt >= B + 1 rounded up to 4)
+        typedef __attribute__((ext_vector_type(4))) int i32x4;
+        const i32x4 t = *reinterpret_cast<const i32x4*>(ix + j0);
+        const f32x4 u = *reinterpret_cast<const f32x4*>(sh + j0);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) tix[i][k] = j0 + k <= B ? t[k] : -2, tsh[i][k] = j0 + k <= B ? u[k] : 0.f;
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const int j = j0 + k;
+          tix[i][k] = j <= B ? ix[j] : -2;
+          tsh[i][k] = j <= B ? sh[j] : 0.f;
+        }
+      }
+    }
+    mx = bar_block_max(mx, red);
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) e[i][k] = expf(e[i][k] - mx);
+    const float inv = 1.0f / bar_block_scan<NV>(e, c, red);
+    // the previous member's gather is done with p_s / c_s: bar_block_scan's barriers lie in between
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int j0 = bar_index<NV>(i);
+      if (j0 < B) {
+        *reinterpret_cast<f32x4*>(p_s + j0) = f32x4{e[i][0], e[i][1], e[i][2], e[i][3]} * inv;
+        *reinterpret_cast<f32x4*>(c_s + j0) = f32x4{c[i][0], c[i][1], c[i][2], c[i][3]} * inv;
+      }
+    }
+    __syncthreads();
+    // CDF of the member's distribution at a target border (utils.py:659-677,696-698) from its table entries
+    auto cdf_of = [&](int s, float share) -> float {
+      if (s < 0) return s == -1 ? 0.0f : 1.0f;
+      s = s < B ? s : B - 1;  // a table entry beyond the bars must not index past the row
+      return fminf(fmaxf(c_s[s] + p_s[s] * share, 0.0f), 1.0f);
+    };
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int j0 = bar_index<NV>(i);
+      float cd[5];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) cd[k] = cdf_of(tix[i][k], tsh[i][k]);
+      cd[4] = __shfl_down(cd[0], 1, 64);
+      if (lane == 63) cd[4] = j0 + 4 <= B ? cdf_of(ix[j0 + 4], sh[j0 + 4]) : 1.0f;  // the next group's first border
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const float bar = fmaxf(cd[k + 1] - cd[k], 0.0f);
+        acc[i][k] += a.avg_before ? logf(bar) : bar;
+      }
+    }
+  }
+
+  // ensemble mean (regressor.py:699-703), then log and the criterion's own softmax (:706, bar_distribution.py:241)
+  const float invM = 1.0f / (float)a.M;
+  float e[NV][4], c[NV][4];
+  if (a.avg_before) {
+    float mx = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        acc[i][k] = bar_index<NV>(i) + k < B ? acc[i][k] * invM : -INFINITY;
+        mx = fmaxf(mx, acc[i][k]);
+      }
+    mx = bar_block_max(mx, red);
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        acc[i][k] = expf(acc[i][k] - mx);
+        s += acc[i][k];
+      }
+    const float inv = 1.0f / bar_block_sum(s, red);
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) acc[i][k] *= inv;
+  } else {
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) acc[i][k] = bar_index<NV>(i) + k < B ? acc[i][k] * invM : 0.f;
+  }
+  float mx = -INFINITY;
+#pragma unroll
+  for (int i = 0; i < NV; ++i)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      acc[i][k] = logf(acc[i][k]);  // the final log-probabilities; -inf beyond B
+      mx = fmaxf(mx, acc[i][k]);
+    }
+  if (a.out_logits) {
+    float* out = a.out_logits + (int64_t)q * B;
+    const bool vec = (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int j0 = bar_index<NV>(i);
+      if (vec && j0 + 3 < B) {
+        *reinterpret_cast<f32x4*>(out + j0) = f32x4{acc[i][0], acc[i][1], acc[i][2], acc[i][3]};
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (j0 + k < B) out[j0 + k] = acc[i][k];
+      }
+    }
+  }
+  mx = bar_block_max(mx, red);
+#pragma unroll
+  for (int i = 0; i < NV; ++i)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) e[i][k] = expf(acc[i][k] - mx);
+  const float inv = 1.0f / bar_block_scan<NV>(e, c, red);
+
+  // mean, mode (first bucket of the largest density), and p / inclusive cumulative sums for the quantiles
+  float msum = 0.f, best = -INFINITY;
+  int best_j = 0x7fffffff;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int j0 = bar_index<NV>(i);
+    float pk[4], ck[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      pk[k] = e[i][k] * inv;
+      ck[k] = (c[i][k] + e[i][k]) * inv;
+      if (j0 + k < B) {
+        msum += pk[k] * a.means[j0 + k];
+        const float dens = pk[k] / a.widths[j0 + k];
+        if (dens > best) best = dens, best_j = j0 + k;  // ascending j within a thread: the first maximum stays
+      }
+    }
+    if (j0 < B) {
+      *reinterpret_cast<f32x4*>(p_s + j0) = f32x4{pk[0], pk[1], pk[2], pk[3]};
+      *reinterpret_cast<f32x4*>(c_s + j0) = f32x4{ck[0], ck[1], ck[2], ck[3]};
+    }
+  }
+  msum = bar_block_sum(msum, red);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ob = __shfl_xor(best, o, 64);
+    const int oj = __shfl_xor(best_j, o, 64);
+    if (ob > best || (ob == best && oj < best_j)) best = ob, best_j = oj;
+  }
+  __syncthreads();
+  if (lane == 0) red[wave] = best, red_i[wave] = best_j;
+  __syncthreads();  // also orders the p_s / c_s stores before the quantile search
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < 4; ++w)
+      if (red[w] > best || (red[w] == best && red_i[w] < best_j)) best = red[w], best_j = red_i[w];
+    a.mean[q] = msum;
+    a.mode[q] = a.mode_means[best_j < B ? best_j : 0];
+  }
+  // icdf (bar_distribution.py:256-283): first bucket whose inclusive cumulative sum reaches the level
+  for (int k = threadIdx.x; k < a.K; k += kBarThreads) {
+    const float lv = a.levels[k];
+    int lo = 0, hi = B;  // lower bound of lv in c_s[0 .. B)
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (c_s[mid] < lv) lo = mid + 1;
+      else hi = mid;
+    }
+    const int j = lo < B - 1 ? lo : B - 1;
+    const float rest = lv - (j > 0 ? c_s[j - 1] : 0.0f);
+    const float left = a.borders[j], right = a.borders[j + 1];
+    a.quantiles[(int64_t)k * a.Q + q] = left + (right - left) * rest / p_s[j];
+  }
+}
+
+template <int NV>
+hipError_t bar_head_launch(const BarHeadArgs& a, hipStream_t st) {
+  const size_t lds = (size_t)2 * ((a.B + 3) & ~3) * sizeof(float);  // 64 KiB at B = 8192, beside the static words
+  if (lds + 64 > 64 * 1024) {
+    static std::atomic<uint64_t> opted{0};
+    const hipError_t e = lds_optin(opted, (const void*)bar_head_kernel<NV>, 64 * 1024);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(bar_head_kernel<NV>, dim3(a.Q), dim3(kBarThreads), lds, st, a);
+  return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_bar_head(const float* logits, int M, int Q, int B, const unsigned char* cancel, int ldc,
+                           const int* idx, const float* share, int ldt, float inv_temp, int avg_before, const float* borders,
+                           const float* means, const float* mode_means, const float* widths, const float* levels,
+                           int K, float* out_logits, float* mean, float* mode, float* quantiles, hipStream_t st) {
+  if (Q <= 0) return hipSuccess;
+  if (M <= 0 || M > kBarHeadMaxMembers || B < 1 || B > kBarHeadMaxBars || K < 0 || K > kBarHeadMaxLevels ||
+      ldt < B + 1 || (cancel && ldc < B))
+    return hipErrorInvalidValue;
+  const int tvec = ldt % 4 == 0 && ldt >= ((B + 4) & ~3) && (reinterpret_cast<uintptr_t>(idx) & 15) == 0 &&
+                   (reinterpret_cast<uintptr_t>(share) & 15) == 0;
+  const int cvec = cancel && ldc % 4 == 0 && ldc >= ((B + 3) & ~3) && (reinterpret_cast<uintptr_t>(cancel) & 3) == 0;
+  const BarHeadArgs a{logits, cancel,  idx,  share, borders, means, mode_means, widths,   levels,
+                      out_logits, mean, mode, quantiles, M,  Q,  B,  K,  inv_temp, avg_before, ldt, ldc, tvec, cvec};
+  if (B <= 1024) return bar_head_launch<1>(a, st);
+  if (B <= 2048) return bar_head_launch<2>(a, st);
+  if (B <= 5120) return bar_head_launch<5>(a, st);
+  return bar_head_launch<8>(a, st);
+}
+
+}  // namespace mmpfn

@@ -43,7 +43,9 @@ struct HeadBank {  // the MGM heads or the MoE experts, stacked
 struct ModelWeights {
   std::vector<LayerW> layers;
   DevBuf enc_w, y_w, y_b, pe_w, pe_b, dec_b1, dec_b2;
-  Weight dec_w1, dec_w2;  // 16-bit forms (the MFMA decoder) only where n_out <= 16 && nhid % 128 == 0
+  // class targets: fp32 forms, and 16-bit forms (the MFMA decoder) only where n_out <= 16 && nhid % 128 == 0; a value
+  // target: natural [Fh][E] / [n_out][Fh] in fp32, bf16 and fp16 (launch_decoder_wide), nothing else
+  Weight dec_w1, dec_w2;
   HeadBank mgm, moe;      // fp16 forms (PREC_F16's MGM head bank) only in mgm_f16_shape
   DevBuf moe_gw, moe_gb;
   Weight cap_kv, cap_o, cap_f0, cap_f3;
@@ -177,8 +179,10 @@ int finalize_encoders_decoder(mmpfn_ctx* ctx, ModelWeights& w) {
   const mmpfn_model_desc& d = ctx->d;
   const int E = d.emsize, Fh = d.nhid, nf = d.encoder_features;
   GETW(ew, d.remove_duplicate_features ? "encoder.6.layer.weight" : "encoder.5.layer.weight", (size_t)E * 2 * nf);
-  GETW(yw, "y_encoder.2.layer.weight", (size_t)E * 2);
-  GETW(yb, "y_encoder.2.layer.bias", (size_t)E);
+  // the Linear step follows the class-code step, which a value target's y encoder does not have (loading.py:374-398)
+  const std::string yl = d.target_kind == MMPFN_TARGET_VALUE ? "y_encoder.1.layer." : "y_encoder.2.layer.";
+  GETW(yw, yl + "weight", (size_t)E * 2);
+  GETW(yb, yl + "bias", (size_t)E);
   GETW(pw, "feature_positional_embedding_embeddings.weight", (size_t)E * (E / 4));
   GETW(pb, "feature_positional_embedding_embeddings.bias", (size_t)E);
   GETW(dw1, "decoder_dict.standard.0.weight", (size_t)Fh * E);
@@ -188,6 +192,11 @@ int finalize_encoders_decoder(mmpfn_ctx* ctx, ModelWeights& w) {
   for (auto [buf, v] : {std::pair{&w.enc_w, ew}, {&w.y_w, yw}, {&w.y_b, yb}, {&w.pe_w, pw}, {&w.pe_b, pb},
                         {&w.dec_b1, db1}, {&w.dec_b2, db2}})
     RC(upload(ctx, *buf, *v));
+  if (d.target_kind == MMPFN_TARGET_VALUE) {  // launch_decoder_wide: both natural, one form per operand type
+    RC(fill(ctx, w.dec_w1, *dw1, Weight::F32 | Weight::BF16 | Weight::F16));
+    RC(fill(ctx, w.dec_w2, *dw2, Weight::F32 | Weight::BF16 | Weight::F16));
+    return MMPFN_OK;
+  }
   RC(fill(ctx, w.dec_w1, transpose_out(*dw1, Fh, E), Weight::F32));  // launch_decoder: W1 [E][Fh], W2 natural
   RC(fill(ctx, w.dec_w2, *dw2, Weight::F32));
   if (d.n_out <= 16 && Fh % 128 == 0) {  // launch_decoder_mfma: W1 natural, W2 zero-padded to [16][Fh] and permuted
@@ -401,7 +410,8 @@ int embed(mmpfn_ctx* ctx, const float* x, int S, int F, const float* tokens, int
           const float* uniq, int U, const float* pos_rand, int precision, int m = 0, int M = 1) {
   const mmpfn_model_desc& d = ctx->d;
   if (!ctx->finalized) return fail(ctx, MMPFN_ERR_STATE, "weights not finalised");
-  if (S <= 0 || N <= 0 || N > S || (x && F <= 0) || C < 0 || U <= 0)
+  const bool value_target = d.target_kind == MMPFN_TARGET_VALUE;  // no class codes: uniq / U unused
+  if (S <= 0 || N <= 0 || N > S || (x && F <= 0) || C < 0 || (!value_target && U <= 0))
     return fail(ctx, MMPFN_ERR_INVALID, "bad forward geometry");
   if (!x && C == 0) return fail(ctx, MMPFN_ERR_INVALID, "no input tokens");
   if (!prec_ok(precision)) return fail(ctx, MMPFN_ERR_INVALID, "bad precision");
@@ -437,7 +447,7 @@ int embed(mmpfn_ctx* ctx, const float* x, int S, int F, const float* tokens, int
   HIPCHK(launch_assemble(x, S, F, G, fpg, d.encoder_features, (const SlotParams*)ctx->ws_slots.p,
                          (const float*)ctx->w.enc_w.p, (const float*)ctx->ws_pe.p, tokens, C, y, N, uniq, U,
                          (const float*)ctx->w.y_w.p, (const float*)ctx->w.y_b.p, (const float*)ctx->ws_scr.p, X,
-                         pm.state(), E, flag, st));
+                         pm.state(), E, flag, st, value_target));
   ctx->embedded = true;
   return MMPFN_OK;
 }
@@ -460,7 +470,8 @@ int embed_cached(mmpfn_ctx* ctx, const mmpfn_cache* cc, const float* x, int S, i
   HIPCHK(launch_assemble(x, S, F, G, fpg, d.encoder_features, (const SlotParams*)cc->slots.p,
                          (const float*)ctx->w.enc_w.p, (const float*)cc->pe.p, tokens, C, nullptr, 0,
                          (const float*)cc->uniq.p, cc->U, (const float*)ctx->w.y_w.p, (const float*)ctx->w.y_b.p,
-                         (const float*)cc->ymean.p, ctx->ws_X.p, lane_prec(*ctx).state(), E, flag, st));
+                         (const float*)cc->ymean.p, ctx->ws_X.p, lane_prec(*ctx).state(), E, flag, st,
+                         d.target_kind == MMPFN_TARGET_VALUE));
   ctx->embedded = true;
   return MMPFN_OK;
 }
@@ -663,6 +674,15 @@ int decode(mmpfn_ctx* ctx, float* logits, int M = 1) {
   const float* Xl = (const float*)ctx->ws_X.p + off;
   int64_t xm = (int64_t)S * T * E;
   const ModelWeights& w = ctx->w;
+  if (d.target_kind == MMPFN_TARGET_VALUE) {  // n_out bars: two GEMMs in the mode's operand type, hidden through ws_O
+    const DType op = pm.is16() ? pm.w16() : DType::F32;
+    RC(ensure(ctx, ctx->ws_O, (size_t)M * Q * d.nhid * pm.op_bytes()));
+    const void* X = (const char*)ctx->ws_X.p + off * pm.state_bytes();
+    HIPCHK(launch_decoder_wide(X, pm.state(), Q, xm, M, pm.is16() ? w.dec_w1.op16(op) : w.dec_w1.f32.p,
+                               (const float*)w.dec_b1.p, d.nhid, pm.is16() ? w.dec_w2.op16(op) : w.dec_w2.f32.p,
+                               (const float*)w.dec_b2.p, d.n_out, op, ctx->ws_O.p, logits, E, ctx->stream));
+    return MMPFN_OK;
+  }
   if (pm.is16() && w.dec_w1.bf16.p) {  // the state as it is (fp32 / fp16) into 16-bit MFMA operands
     const void* X = (const char*)ctx->ws_X.p + off * pm.state_bytes();
     HIPCHK(launch_decoder_mfma(X, pm.state(), Q, w.dec_w1.op16(pm.w16()), (const float*)w.dec_b1.p, d.nhid,
@@ -911,6 +931,8 @@ int mmpfn_set_model(mmpfn_ctx* ctx, const mmpfn_model_desc* desc) {
   if (d.nhid % 192 != 0 || d.nlayers <= 0 || d.features_per_group <= 0 || d.features_per_group > 8 ||
       d.encoder_features < d.features_per_group || d.encoder_features > 8 || d.n_out <= 0)
     return fail(ctx, MMPFN_ERR_INVALID, "unsupported model geometry");
+  if (d.target_kind != MMPFN_TARGET_CLASS && d.target_kind != MMPFN_TARGET_VALUE)
+    return fail(ctx, MMPFN_ERR_INVALID, "target_kind " + std::to_string(d.target_kind) + ": not an MMPFN_TARGET_* code");
   // the head banks' down-projection contracts over K = nhid / 2, in 64-wide slices in the bf16 and split-bf16 GEMMs
   if (d.mixer_type != MMPFN_MIXER_NONE && (d.nhid / 2) % 64 != 0)
     return fail(ctx, MMPFN_ERR_INVALID,
@@ -1004,11 +1026,13 @@ int mmpfn_forward(mmpfn_ctx* ctx, const float* x, int S, int F, const float* tok
 int mmpfn_forward_batch(mmpfn_ctx* ctx, int M, const float* const* x, int S, int F, const float* tokens, int C,
                         const float* const* y, int N, const float* const* uniq, const int* U, const float* pos_rand,
                         float* logits, int precision) {
-  if (!ctx || !logits || M <= 0 || !y || !uniq || !U) return MMPFN_ERR_INVALID;
+  const bool codes = ctx && ctx->d.target_kind == MMPFN_TARGET_CLASS;  // a value target reads neither uniq nor U
+  if (!ctx || !logits || M <= 0 || !y || (codes && (!uniq || !U))) return MMPFN_ERR_INVALID;
   if (F > 0 && !x) return MMPFN_ERR_INVALID;
   HIPCHK(hipSetDevice(ctx->device));
   for (int m = 0; m < M; ++m)
-    RC(embed(ctx, F > 0 ? x[m] : nullptr, S, F, tokens, C, y[m], N, uniq[m], U[m], pos_rand, precision, m, M));
+    RC(embed(ctx, F > 0 ? x[m] : nullptr, S, F, tokens, C, y[m], N, codes ? uniq[m] : nullptr, codes ? U[m] : 0, pos_rand,
+             precision, m, M));
   RC(run_forward_layers(ctx));
   return decode(ctx, logits, M);
 }
@@ -1036,6 +1060,30 @@ int mmpfn_aggregate(mmpfn_ctx* ctx, const float* logits, int M, int Q, int n_out
     return MMPFN_ERR_INVALID;
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(launch_aggregate(logits, M, Q, n_out, perms, n_cls, temperature, avg_before, cw, probs, ctx->stream));
+  return MMPFN_OK;
+}
+
+static_assert(MMPFN_BAR_MAX_BARS == kBarHeadMaxBars && MMPFN_BAR_MAX_MEMBERS == kBarHeadMaxMembers &&
+                  MMPFN_BAR_MAX_LEVELS == kBarHeadMaxLevels,
+              "the header's mmpfn_bar_head limits are the kernel's");
+
+int mmpfn_bar_head(mmpfn_ctx* ctx, const float* logits, int M, int Q, int B, const unsigned char* cancel, int ldc,
+                   const int* idx, const float* share, int ldt, float inv_temperature, int avg_before, const float* borders,
+                   const float* bucket_means, const float* mode_means, const float* widths, const float* levels, int K,
+                   float* out_logits, float* mean, float* mode, float* quantiles) {
+  if (!ctx) return MMPFN_ERR_INVALID;
+  if (!logits || !idx || !share || !borders || !bucket_means || !mode_means || !widths || !mean || !mode || Q < 0 ||
+      K < 0 || (K > 0 && (!levels || !quantiles)) || !(inv_temperature > 0.f))
+    return fail(ctx, MMPFN_ERR_INVALID, "mmpfn_bar_head: null argument, negative size or temperature <= 0");
+  if (ldt < B + 1 || (cancel && ldc < B))
+    return fail(ctx, MMPFN_ERR_INVALID, "mmpfn_bar_head: ldt < B + 1 or ldc < B");
+  if (B < 1 || B > MMPFN_BAR_MAX_BARS || M < 1 || M > MMPFN_BAR_MAX_MEMBERS || K > MMPFN_BAR_MAX_LEVELS)
+    return fail(ctx, MMPFN_ERR_INVALID,
+                "mmpfn_bar_head: B, M or K beyond the kernel (B " + std::to_string(B) + ", M " + std::to_string(M) +
+                    ", K " + std::to_string(K) + ")");
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(launch_bar_head(logits, M, Q, B, cancel, ldc, idx, share, ldt, inv_temperature, avg_before, borders, bucket_means,
+                         mode_means, widths, levels, K, out_logits, mean, mode, quantiles, ctx->stream));
   return MMPFN_OK;
 }
 
@@ -1094,7 +1142,9 @@ int mmpfn_item_attention(mmpfn_ctx* ctx, const void* q, const void* k, const voi
 
 int mmpfn_cache_build(mmpfn_ctx* ctx, const float* x, int N, int F, const float* tokens, int C, const float* y_train,
                       const float* uniq, int U, const float* pos_rand, int precision, mmpfn_cache** out) {
-  if (!ctx || !out || !y_train || !uniq || !pos_rand) return MMPFN_ERR_INVALID;
+  if (!ctx || !out || !y_train || !pos_rand) return MMPFN_ERR_INVALID;
+  if (ctx->d.target_kind == MMPFN_TARGET_VALUE) uniq = nullptr, U = 0;  // no class codes to keep
+  else if (!uniq) return MMPFN_ERR_INVALID;
   *out = nullptr;
   HIPCHK(hipSetDevice(ctx->device));
   if (!prec_ok(precision)) return fail(ctx, MMPFN_ERR_INVALID, "bad precision");
@@ -1110,13 +1160,13 @@ int mmpfn_cache_build(mmpfn_ctx* ctx, const float* x, int N, int F, const float*
     RC(ensure(ctx, cc->kv, (size_t)d.nlayers * 2 * cc->T * cc->Npad * 32 * eb));
     RC(ensure(ctx, cc->slots, (size_t)(cc->G + 1) * fpg * sizeof(SlotParams)));
     RC(ensure(ctx, cc->ymean, 4));
-    RC(ensure(ctx, cc->uniq, (size_t)U * 4));
+    if (U) RC(ensure(ctx, cc->uniq, (size_t)U * 4));
     RC(ensure(ctx, cc->pe, (size_t)(cc->G + C + 1) * E * 4));
     if (cc->G)
       HIPCHK(hipMemcpyAsync(cc->slots.p, ctx->ws_slots.p, (size_t)cc->G * fpg * sizeof(SlotParams),
                             hipMemcpyDeviceToDevice, st));
     HIPCHK(hipMemcpyAsync(cc->ymean.p, ctx->ws_scr.p, 4, hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemcpyAsync(cc->uniq.p, uniq, (size_t)U * 4, hipMemcpyDeviceToDevice, st));
+    if (U) HIPCHK(hipMemcpyAsync(cc->uniq.p, uniq, (size_t)U * 4, hipMemcpyDeviceToDevice, st));
     HIPCHK(hipMemcpyAsync(cc->pe.p, ctx->ws_pe.p, (size_t)(cc->G + C) * E * 4, hipMemcpyDeviceToDevice, st));
     ctx->cache_out = cc;
     const int rc = run_forward_layers(ctx);

@@ -256,6 +256,7 @@ struct AsmArgs {
   int N;
   const float* uniq;
   int U;
+  int value_target;  // the label token's first input is the target itself, not its class code (uniq unused)
   const float *yw, *yb, *ymean;
   void* X;
   int E;
@@ -296,7 +297,10 @@ __global__ __launch_bounds__(256) void assemble_kernel(const AsmArgs a) {
       float yv = s < a.N ? a.y[s] : NAN;
       ind = isnan(yv) ? -2.0f : 0.0f;
       if (isnan(yv)) yv = a.ymean[0];
-      for (int i2 = 0; i2 < a.U; ++i2) u += (yv > a.uniq[i2]) ? 1.f : 0.f;
+      if (a.value_target)
+        u = yv;
+      else
+        for (int i2 = 0; i2 < a.U; ++i2) u += (yv > a.uniq[i2]) ? 1.f : 0.f;
     }
     su[i][k] = u, si[i][k] = ind;
   }
@@ -605,7 +609,7 @@ hipError_t launch_encode_stats(const float* x, int S, int F, int N, int G, int f
 hipError_t launch_assemble(const float* x, int S, int F, int G, int fpg, int nf, const SlotParams* slots,
                            const float* w_enc, const float* posemb, const float* tok, int C, const float* y, int N,
                            const float* uniq, int U, const float* yw, const float* yb, const float* ymean, void* X,
-                           DType x_t, int E, int* flag, hipStream_t st) {
+                           DType x_t, int E, int* flag, hipStream_t st, bool value_target) {
   if (S <= 0 || G < 0 || C < 0 || U < 0 || N < 0 || N > S || x_t == DType::BF16) return hipErrorInvalidValue;
   const bool half = x_t == DType::F16;
   if ((G > 0 && (!x || !slots || fpg <= 0 || fpg > 8 || nf > 8 || nf < fpg)) || (C > 0 && !tok) || (N > 0 && !y))
@@ -613,7 +617,8 @@ hipError_t launch_assemble(const float* x, int S, int F, int G, int fpg, int nf,
   if (E > EMB_EMAX || E % (half ? 8 : 4) != 0 || (int64_t)(G + C + 1) * S >= INT32_MAX / 2) return hipErrorInvalidValue;
   AsmArgs a;
   a.x = x, a.S = S, a.F = F, a.G = G, a.fpg = fpg, a.nf = nf, a.slots = slots, a.w_enc = w_enc, a.pe = posemb;
-  a.tok = tok, a.C = C, a.y = y, a.N = N, a.uniq = uniq, a.U = U, a.yw = yw, a.yb = yb, a.ymean = ymean;
+  a.tok = tok, a.C = C, a.y = y, a.N = N, a.yw = yw, a.yb = yb, a.ymean = ymean;
+  a.uniq = value_target ? nullptr : uniq, a.U = value_target ? 0 : U, a.value_target = value_target;
   a.X = X, a.E = E, a.flag = flag;
   const int nb = (int)(((int64_t)(G + C + 1) * S + ASM_ROWS - 1) / ASM_ROWS);
   if (half)

@@ -252,7 +252,7 @@ hipError_t launch_assemble(const float* x, int S, int F, int G, int fpg, int nf,
                            const float* w_enc /*[E][2nf]*/, const float* posemb /*[G+C][E]*/,
                            const float* tok /*[S][C][E]*/, int C, const float* y, int N, const float* uniq, int U,
                            const float* yw /*[E][2]*/, const float* yb, const float* ymean, void* X, DType x_t, int E,
-                           int* flag, hipStream_t st);
+                           int* flag, hipStream_t st, bool value_target = false);  // value_target: uniq / U unused
 hipError_t launch_pos_emb(const float* rnd /*[n][E/4]*/, int n, const float* w /*[E][E/4]*/,
                           const float* b, float* out /*[n][E]*/, int E, hipStream_t st);
 // M members' decoders: X + m*xm [Q][E] -> out + m*om [Q][n_out]; scratch >= M*(Fh/64)*Q*n_out floats
@@ -265,6 +265,12 @@ hipError_t launch_decoder(const float* X /*[Q][E]*/, int Q, const float* w1t /*[
 hipError_t launch_decoder_mfma(const void* X, DType x_t, int Q, const void* W1, const float* b1, int Fh, const void* W2p,
                                const float* b2, int n_out, float* out, int E, hipStream_t st, int M, int64_t xm,
                                int64_t om);
+// the value-target decoder (decoder_wide.hip), any n_out: X + m*xm [Q][E] in x_t -> hidden [M*Q][Fh] in op_t (a
+// workspace) -> out [M][Q][n_out] fp32; W1 [Fh][E] and W2 [n_out][Fh] natural, in op_t.  (x_t, op_t): (F32, F32) on
+// fp32-input MFMA, (F32, BF16), (F16, F16); E % 32 == 0, Fh % 32 == 0
+hipError_t launch_decoder_wide(const void* X, DType x_t, int Q, int64_t xm, int M, const void* W1, const float* b1,
+                               int Fh, const void* W2, const float* b2, int n_out, DType op_t, void* hidden, float* out,
+                               int E, hipStream_t st);
 // PREC_F16 state conversions: nb blocks of per_block elements (per_block % 4 == 0) at the given block
 // strides (elements); the state [T][S][E] fp16 -> the reference order [S][T][E] fp32
 hipError_t launch_f32_to_f16(const float* in, int64_t in_bstride, void* out, int64_t out_bstride, int64_t per_block,
@@ -276,6 +282,16 @@ hipError_t launch_state_f16_to_f32(const void* X, float* out, int S, int T, int 
 hipError_t launch_aggregate(const float* logits /*[M][Q][n_out]*/, int M, int Q, int n_out,
                             const int* perms /*[M][n_cls] or null*/, int n_cls, float temp, int avg_before,
                             const float* class_weights /*[n_cls] or null*/, float* probs, hipStream_t st);
+
+// Bar-distribution head (barhead.hip): M members' logits [M][Q][B] -> the ensemble's final log-probabilities [Q][B]
+// (null: not stored), mean / mode [Q] and quantiles [K][Q] under the renormalised criterion.  idx / share [M][ldt]
+// (ldt >= B + 1) are the host's per-border tables (idx -1 / -2: the CDF forced to 0 / 1); cancel [M][ldc] bytes
+// (ldc >= B) or null.  Rows padded to a multiple of 4 entries (and 16-byte bases) are read in 16- / 4-byte pieces.
+constexpr int kBarHeadMaxBars = 8192, kBarHeadMaxMembers = 1024, kBarHeadMaxLevels = 64;
+hipError_t launch_bar_head(const float* logits, int M, int Q, int B, const unsigned char* cancel, int ldc,
+                           const int* idx, const float* share, int ldt, float inv_temp, int avg_before, const float* borders,
+                           const float* means, const float* mode_means, const float* widths, const float* levels,
+                           int K, float* out_logits, float* mean, float* mode, float* quantiles, hipStream_t st);
 
 // ---- mixer helpers -----------------------------------------------------------------
 hipError_t launch_layernorm_rows(const float* in, int64_t rows, int dim, float eps, void* out, DType out_t,

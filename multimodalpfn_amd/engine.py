@@ -21,11 +21,15 @@ import numpy as np
 import torch
 
 from multimodalpfn_amd import _lib
-from multimodalpfn_amd.model.spec import ModelConfig, encoder_linear_name
+from multimodalpfn_amd.model.spec import CRITERION_PREFIX, ModelConfig, encoder_linear_name
 
 
 def _ptr(t: torch.Tensor | None) -> int | None:
     return None if t is None else t.data_ptr()
+
+
+def _count(t: torch.Tensor | None) -> int:
+    return 0 if t is None else t.numel()
 
 
 def model_desc(cfg: ModelConfig) -> _lib.ModelDesc:
@@ -44,6 +48,7 @@ def model_desc(cfg: ModelConfig) -> _lib.ModelDesc:
     d.remove_duplicate_features = int(cfg.remove_duplicate_features)
     d.ln_eps = cfg.ln_eps
     d.outlier_sigma = float(cfg.remove_outliers_sigma) if cfg.remove_outliers_sigma else 0.0
+    d.target_kind = _lib.TARGET_VALUE if cfg.is_regression else _lib.TARGET_CLASS
     return d
 
 
@@ -132,6 +137,8 @@ class HipEngine:
         self._check(self.lib.mmpfn_set_model(self.ctx, ctypes.byref(self.desc)), "mmpfn_set_model")
         names = set()
         for name, t in state_dict.items():
+            if name.startswith(CRITERION_PREFIX):  # the bar distribution's buffers stay on the host
+                continue
             if isinstance(t, torch.Tensor):
                 a = t.detach().to("cpu", torch.float32).contiguous().numpy()
             else:
@@ -243,7 +250,8 @@ class HipEngine:
             raise ValueError(f"tokens rows {td.shape[0]} != table rows {S}")
         fpg = self.cfg.features_per_group
         G = (F + fpg - 1) // fpg if xd is not None else 0
-        uniq = self._dev(torch.from_numpy(target_uniques(y_np)))
+        # a value target has no class codes: nothing to compute or upload (the engine ignores uniq / U)
+        uniq = None if self.cfg.is_regression else self._dev(torch.from_numpy(target_uniques(y_np)))
         yd = self._dev(torch.from_numpy(y_np))
         if _DEBUG_KEEP:
             _KEEP.append((xd, td, yd, uniq))
@@ -259,7 +267,7 @@ class HipEngine:
         self._bind_stream()
         self._check(
             self.lib.mmpfn_forward(
-                self.ctx, _ptr(xd), S, F, _ptr(td), C, _ptr(yd), N, _ptr(uniq), uniq.numel(), _ptr(pr), _ptr(out),
+                self.ctx, _ptr(xd), S, F, _ptr(td), C, _ptr(yd), N, _ptr(uniq), _count(uniq), _ptr(pr), _ptr(out),
                 precision,
             ),
             "mmpfn_forward",
@@ -280,7 +288,7 @@ class HipEngine:
         h = ctypes.c_void_p()
         self._bind_stream()
         self._check(
-            self.lib.mmpfn_cache_build(self.ctx, _ptr(xd), N, F, _ptr(td), C, _ptr(yd), _ptr(uniq), uniq.numel(),
+            self.lib.mmpfn_cache_build(self.ctx, _ptr(xd), N, F, _ptr(td), C, _ptr(yd), _ptr(uniq), _count(uniq),
                                        _ptr(pr), precision, ctypes.byref(h)),
             "mmpfn_cache_build",
         )
@@ -351,7 +359,7 @@ class HipEngine:
         xs = arr(*[_ptr(p[0]) for p in prep]) if F > 0 else None
         ys = arr(*[_ptr(p[2]) for p in prep])
         us = arr(*[_ptr(p[3]) for p in prep])
-        ns = (ctypes.c_int * M)(*[p[3].numel() for p in prep])
+        ns = (ctypes.c_int * M)(*[_count(p[3]) for p in prep])
         self._bind_stream()
         self._check(
             self.lib.mmpfn_forward_batch(self.ctx, M, xs, S, F, _ptr(td), C, ys, N, us, ns, _ptr(pr), _ptr(out),
@@ -484,6 +492,52 @@ class HipEngine:
         )
         return out
 
+    def bar_head(self, logits: torch.Tensor, idx, share, criterion: dict, *, cancel=None,
+                 softmax_temperature: float = 1.0, average_before_softmax: bool = False, quantiles=(),
+                 want_logits: bool = False) -> dict:
+        """Regression post-processing of regressor.py:652-765 on the device (``mmpfn_bar_head``).
+
+        ``logits`` ``[M, Q, B]``; ``idx`` / ``share`` ``[M, B + 1]`` from ``bar_distribution.border_tables``;
+        ``cancel`` ``[M, B]`` bool or ``None``; ``criterion``: ``FullSupportBarDistribution.head_tables()`` of the
+        renormalised criterion.  Returns device tensors ``mean`` / ``mode`` ``[Q]``, ``quantiles`` ``[K, Q]`` and
+        ``logits`` ``[Q, B]`` (``None`` unless ``want_logits``)."""
+        lg = logits.to(self.device, torch.float32).contiguous()
+        M, Q, B = lg.shape
+        if B > _lib.BAR_MAX_BARS or M > _lib.BAR_MAX_MEMBERS or len(quantiles) > _lib.BAR_MAX_LEVELS or B < 1 or M < 1:
+            raise ValueError(f"mmpfn_bar_head holds 1..{_lib.BAR_MAX_BARS} bars, 1..{_lib.BAR_MAX_MEMBERS} members and "
+                             f"{_lib.BAR_MAX_LEVELS} levels; got {B}, {M}, {len(quantiles)}")
+        if not softmax_temperature > 0:
+            raise ValueError(f"softmax_temperature must be > 0, got {softmax_temperature}")
+        # rows padded to a multiple of 4 entries: the kernel then reads them in 16-byte (tables) / 4-byte (mask) pieces
+        ldt, ldc = (B + 4) & ~3, (B + 3) & ~3
+        ix_h = np.full((M, ldt), -2, dtype=np.int32)
+        ix_h[:, :B + 1] = np.asarray(idx, dtype=np.int32).reshape(M, B + 1)
+        sh_h = np.zeros((M, ldt), dtype=np.float32)
+        sh_h[:, :B + 1] = np.asarray(share, dtype=np.float32).reshape(M, B + 1)
+        ix, sh, cm = self._dev(ix_h, torch.int32), self._dev(sh_h), None
+        if cancel is not None:
+            cm_h = np.zeros((M, ldc), dtype=np.uint8)
+            cm_h[:, :B] = np.asarray(cancel, dtype=np.uint8).reshape(M, B)
+            cm = self._dev(cm_h, torch.uint8)
+        tabs = {k: self._dev(criterion[k]).reshape(-1) for k in ("borders", "bucket_means", "mode_means", "widths")}
+        if tabs["borders"].numel() != B + 1 or any(tabs[k].numel() != B for k in ("bucket_means", "mode_means", "widths")):
+            raise ValueError(f"criterion tables do not fit {B} bars")
+        K = len(quantiles)
+        lv = self._dev(np.asarray(quantiles, dtype=np.float32)) if K else None
+        out = torch.empty((Q, B), device=self.device, dtype=torch.float32) if want_logits else None
+        mean = torch.empty((Q,), device=self.device, dtype=torch.float32)
+        mode = torch.empty((Q,), device=self.device, dtype=torch.float32)
+        qs = torch.empty((K, Q), device=self.device, dtype=torch.float32)
+        self._bind_stream()
+        self._check(
+            self.lib.mmpfn_bar_head(self.ctx, _ptr(lg), M, Q, B, _ptr(cm), ldc, _ptr(ix), _ptr(sh), ldt,
+                                    1.0 / float(softmax_temperature), int(average_before_softmax), _ptr(tabs["borders"]),
+                                    _ptr(tabs["bucket_means"]), _ptr(tabs["mode_means"]), _ptr(tabs["widths"]), _ptr(lv),
+                                    K, _ptr(out), _ptr(mean), _ptr(mode), _ptr(qs) if K else None),
+            "mmpfn_bar_head",
+        )
+        return {"mean": mean, "mode": mode, "quantiles": qs, "logits": out}
+
     def status(self) -> None:
         """Wait for every stream the context ran on and raise ``ValueError`` if any forward since the
         last call saw NaNs in its embedded input (transformer.py:727-731,790-796)."""
@@ -499,7 +553,7 @@ class HipEngine:
         self._bind_stream()
         self._check(
             self.lib.mmpfn_embed(
-                self.ctx, _ptr(xd), S, F, _ptr(td), C, _ptr(yd), N, _ptr(uniq), uniq.numel(), _ptr(pr), precision
+                self.ctx, _ptr(xd), S, F, _ptr(td), C, _ptr(yd), N, _ptr(uniq), _count(uniq), _ptr(pr), precision
             ),
             "mmpfn_embed",
         )

@@ -26,7 +26,8 @@ from typing import Any
 import torch
 from torch import nn
 
-from multimodalpfn_amd.model.spec import ModelConfig, state_dict_spec
+from multimodalpfn_amd.bar_distribution import FullSupportBarDistribution
+from multimodalpfn_amd.model.spec import CRITERION_PREFIX, ModelConfig, criterion_spec, state_dict_spec
 from multimodalpfn_amd.model.transformer import PerFeatureTransformer
 
 # InferenceConfig fields read by the forward; the rest only matter for training
@@ -69,8 +70,11 @@ def model_config_from_checkpoint(config: dict, *, model_seed: int, mixer_type: s
         if key in config and config[key] is not None and config[key] != want:
             raise NotImplementedError(f"checkpoint config {key}={config[key]!r} (engine implements {want!r})")
     max_classes = int(config.get("max_num_classes", 10))
-    if max_classes == 0:
-        raise NotImplementedError("regression checkpoints (bar-distribution decoder) are not served")
+    num_buckets = 0
+    if max_classes == 0:  # a regression checkpoint: n_out = the criterion's bars (loading.py:264-272,465-468)
+        num_buckets = int(config.get("num_buckets") or 0)
+        if num_buckets < 1:
+            raise ValueError(f"regression checkpoint config needs num_buckets >= 1, got {config.get('num_buckets')!r}")
     return ModelConfig(
         emsize=int(config.get("emsize", 192)),
         nhead=int(config.get("nhead", 6)),
@@ -88,6 +92,7 @@ def model_config_from_checkpoint(config: dict, *, model_seed: int, mixer_type: s
         # the classifier switches it on afterwards (update_encoder_outlier_params)
         remove_outliers_sigma=None,
         model_seed=model_seed,
+        num_buckets=num_buckets,
     )
 
 
@@ -121,7 +126,7 @@ def build_model(cfg: ModelConfig, state_dict: dict[str, Any]) -> PerFeatureTrans
     (loading.py:540): extra keys ignored, missing modality-head tensors keep their (seeded)
     initialisation with a warning, a missing trunk tensor is an error."""
     model = PerFeatureTransformer(cfg)
-    names = [n for n, _ in state_dict_spec(cfg)]
+    names = [n for n, _ in state_dict_spec(cfg) if not n.startswith(CRITERION_PREFIX)]
     missing = [n for n in names if n not in state_dict]
     trunk = [n for n in missing if not n.startswith(MIXER_PREFIXES)]
     if trunk:
@@ -139,7 +144,7 @@ def build_model(cfg: ModelConfig, state_dict: dict[str, Any]) -> PerFeatureTrans
 
 
 def load_model(*, path: Path, model_seed: int, mixer_type: str, mgm_heads: int, cap_heads: int,
-               features_per_group: int) -> tuple[PerFeatureTransformer, nn.Module, dict]:
+               features_per_group: int) -> tuple[PerFeatureTransformer, Any, dict]:
     """``loading.py:401-542``: returns (model, loss criterion, config dict)."""
     ckpt = torch.load(path, map_location="cpu", weights_only=True)
     assert "state_dict" in ckpt
@@ -149,6 +154,21 @@ def load_model(*, path: Path, model_seed: int, mixer_type: str, mgm_heads: int, 
                                        cap_heads=cap_heads, features_per_group=features_per_group)
     state = {k: v for k, v in ckpt["state_dict"].items() if not k.startswith("criterion.")}
     model = build_model(cfg, state)
-    criterion: nn.Module = (nn.BCEWithLogitsLoss(reduction="none") if cfg.max_num_classes == 2
-                            else nn.CrossEntropyLoss(reduction="none"))
+    if cfg.is_regression:
+        criterion = load_bar_distribution(cfg, ckpt["state_dict"])
+    else:
+        criterion = (nn.BCEWithLogitsLoss(reduction="none") if cfg.max_num_classes == 2
+                     else nn.CrossEntropyLoss(reduction="none"))
     return model, criterion, config
+
+
+def load_bar_distribution(cfg: ModelConfig, state_dict: dict[str, Any]) -> FullSupportBarDistribution:
+    """The regression criterion from the checkpoint's ``criterion.borders`` (loading.py:435-442: the dummy borders
+    of ``get_loss_criterion`` are overwritten by the file's, which must have their shape)."""
+    (name, shape), _ = criterion_spec(cfg)
+    if name not in state_dict:
+        raise ValueError(f"regression checkpoint lacks {name}")
+    borders = torch.as_tensor(state_dict[name]).detach().to("cpu", torch.float32)
+    if tuple(borders.shape) != shape:
+        raise ValueError(f"{name} has shape {tuple(borders.shape)}, the config's num_buckets wants {shape}")
+    return FullSupportBarDistribution(borders)

@@ -25,7 +25,7 @@ class ModelConfig:
     nhid_factor: int = 4
     features_per_group: int = 2  # model grouping (PerFeatureTransformer arg, yaml)
     encoder_features: int = 2  # checkpoint config.features_per_group (get_encoder num_features)
-    max_num_classes: int = 10
+    max_num_classes: int = 10  # 0: a regression model -- a real-valued target and num_buckets decoder outputs
     mixer_type: str = "MGM+CAP"  # "MGM" | "MGM+CAP" | "MoE"
     mgm_heads: int = 64
     cap_heads: int = 24
@@ -37,6 +37,7 @@ class ModelConfig:
     remove_outliers_sigma: float | None = 12.0
     model_seed: int = 0
     ln_eps: float = 1e-5
+    num_buckets: int = 0  # bars of the regression criterion (checkpoint config.num_buckets); read with max_num_classes == 0
     extra: dict = field(default_factory=dict)
 
     @property
@@ -49,8 +50,15 @@ class ModelConfig:
 
     @property
     def n_out(self) -> int:
-        # loading.py:460-468 (classifier: max_num_classes > 2 -> n_out = max_num_classes)
+        # loading.py:460-468 (max_num_classes > 2 -> n_out = max_num_classes; 0 -> the criterion's bars)
+        if self.is_regression:
+            return self.num_buckets
         return 1 if self.max_num_classes == 2 else self.max_num_classes
+
+    @property
+    def is_regression(self) -> bool:
+        """A real-valued target: no class-code step in the y encoder, a bar-distribution criterion."""
+        return self.max_num_classes == 0
 
     @property
     def mixer_in_dim(self) -> int:
@@ -60,6 +68,23 @@ class ModelConfig:
 
 def encoder_linear_name(cfg: ModelConfig) -> str:
     return f"encoder.{6 if cfg.remove_duplicate_features else 5}.layer.weight"
+
+
+def y_linear_prefix(cfg: ModelConfig) -> str:
+    """The y encoder's Linear step: index 2 behind the class-code step, index 1 without it (loading.py:374-398)."""
+    return f"y_encoder.{1 if cfg.is_regression else 2}.layer"
+
+
+CRITERION_PREFIX = "criterion."
+
+
+def criterion_spec(cfg: ModelConfig) -> list[tuple[str, tuple[int, ...]]]:
+    """The bar distribution's buffers a regression checkpoint carries beside the model (loading.py:264-272,
+    435-442); nothing for a classifier."""
+    if not cfg.is_regression:
+        return []
+    B = cfg.num_buckets
+    return [(CRITERION_PREFIX + "borders", (B + 1,)), (CRITERION_PREFIX + "losses_per_bucket", (B,))]
 
 
 def state_dict_spec(cfg: ModelConfig) -> list[tuple[str, tuple[int, ...]]]:
@@ -112,8 +137,8 @@ def state_dict_spec(cfg: ModelConfig) -> list[tuple[str, tuple[int, ...]]]:
         spec += [("moe.gate.weight", (cfg.mgm_heads, D)), ("moe.gate.bias", (cfg.mgm_heads,))]
     spec += [
         (encoder_linear_name(cfg), (E, 2 * nf)),
-        ("y_encoder.2.layer.weight", (E, 2)),
-        ("y_encoder.2.layer.bias", (E,)),
+        (y_linear_prefix(cfg) + ".weight", (E, 2)),
+        (y_linear_prefix(cfg) + ".bias", (E,)),
     ]
     for l in range(cfg.nlayers):
         p = f"transformer_encoder.layers.{l}"
@@ -141,4 +166,4 @@ def state_dict_spec(cfg: ModelConfig) -> list[tuple[str, tuple[int, ...]]]:
         ("feature_positional_embedding_embeddings.weight", (E, E // 4)),
         ("feature_positional_embedding_embeddings.bias", (E,)),
     ]
-    return spec
+    return spec + criterion_spec(cfg)

@@ -219,9 +219,10 @@ class PerFeatureTransformer(nn.Module):
             LinearInputEncoderStep(2 * nf, E, bias=False),
         ]
         self.encoder = SequentialEncoder(*steps)
-        self.y_encoder = SequentialEncoder(
-            NanHandlingEncoderStep(True), MulticlassClassificationTargetEncoder(), LinearInputEncoderStep(2, E, True)
-        )
+        y_steps = [NanHandlingEncoderStep(True)]
+        if not cfg.is_regression:  # a real-valued target is embedded as it is (loading.py:387-388)
+            y_steps.append(MulticlassClassificationTargetEncoder())
+        self.y_encoder = SequentialEncoder(*y_steps, LinearInputEncoderStep(2, E, True))
         self.transformer_encoder = LayerStack(cfg)
         self.decoder_dict = nn.ModuleDict(
             {"standard": nn.Sequential(nn.Linear(E, cfg.nhid), nn.GELU(), nn.Linear(cfg.nhid, cfg.n_out))}

@@ -12,8 +12,8 @@ from __future__ import annotations
 
 from collections.abc import Iterable, Iterator, Sequence
 from dataclasses import dataclass
-from itertools import chain, repeat
-from typing import Literal, TypeVar
+from itertools import chain, product, repeat
+from typing import Any, Literal, TypeVar
 
 import numpy as np
 
@@ -76,6 +76,19 @@ def default_classifier_preprocessor_configs() -> list[PreprocessorConfig]:
             subsample_features=-1,
         ),
         PreprocessorConfig("none", categorical_name="numeric", subsample_features=-1),
+    ]
+
+
+def default_regressor_preprocessor_configs() -> list[PreprocessorConfig]:
+    """``preprocessing.py:159-169``."""
+    return [
+        PreprocessorConfig(
+            "quantile_uni",
+            append_original=True,
+            categorical_name="ordinal_very_common_categories_shuffled",
+            global_transformer_name="svd",
+        ),
+        PreprocessorConfig("safepower", categorical_name="onehot"),
     ]
 
 
@@ -167,6 +180,52 @@ class EnsembleConfig:
             for fs, pc, sub, cp in zip(featshifts, pcfgs, subsamples, class_perms)
         ]
 
+    @classmethod
+    def generate_for_regression(
+        cls,
+        *,
+        n: int,
+        subsample_size: int | float | None,
+        max_index: int,
+        add_fingerprint_feature: bool,
+        polynomial_features: Literal["no", "all"] | int,
+        feature_shift_decoder: Literal["shuffle", "rotate"] | None,
+        preprocessor_configs: Sequence[PreprocessorConfig],
+        target_transforms: Sequence[Any],
+        random_state,
+    ) -> list[RegressorEnsembleConfig]:
+        """``preprocessing.py:338-415``: feature shifts, sub-samples, then every (preprocessor, target transform)
+        pair equally often and the remainder drawn -- the reference's draws in the reference's order."""
+        static_seed, rng = infer_random_state(random_state)
+        start = rng.integers(0, MAXIMUM_FEATURE_SHIFT)
+        featshifts = rng.choice(np.arange(start, start + n), size=n, replace=False)
+
+        if isinstance(subsample_size, (int, float)):
+            subsamples = generate_index_permutations(n=n, max_index=max_index, subsample=subsample_size,
+                                                     random_state=static_seed)
+        elif subsample_size is None:
+            subsamples = [None] * n
+        else:
+            raise ValueError(f"Invalid subsample_samples: {subsample_size}")
+
+        combos = list(product(preprocessor_configs, target_transforms))
+        picked = balance(combos, n // len(combos))
+        leftover = n % len(combos)
+        if leftover > 0:
+            picked += [combos[i] for i in rng.choice(len(combos), size=leftover)]
+        return [
+            RegressorEnsembleConfig(
+                preprocess_config=pc,
+                feature_shift_count=fs,
+                add_fingerprint_feature=add_fingerprint_feature,
+                polynomial_features=polynomial_features,
+                feature_shift_decoder=feature_shift_decoder,
+                subsample_ix=sub,
+                target_transform=tt,
+            )
+            for fs, sub, (pc, tt) in zip(featshifts, subsamples, picked)
+        ]
+
     def to_pipeline(self, *, random_state) -> SequentialFeatureTransformer:
         """Steps: [polynomial] -> constant removal -> distribution reshape -> categorical
         encode -> [fingerprint] -> column shuffle (``preprocessing.py:416-473``)."""
@@ -206,15 +265,27 @@ class ClassifierEnsembleConfig(EnsembleConfig):
     class_permutation: np.ndarray | None
 
 
+@dataclass
+class RegressorEnsembleConfig(EnsembleConfig):
+    """Member config with the transform of its target, fitted with the member (``preprocessing.py:491-498``)."""
+
+    target_transform: Any | None
+
+
 def fit_preprocessing_one(config: EnsembleConfig, X_train, y_train, random_state=None, *, cat_ix: list[int]):
-    """Permute labels, sub-sample rows, fit the member pipeline (``preprocessing.py:494-546``).
+    """Permute labels (a classifier's member) or fit and apply the target transform (a regressor's), sub-sample
+    rows, fit the member pipeline (``preprocessing.py:501-560``).
 
     Returns (config, fitted pipeline | None, X_train', y_train', categorical indices).
     """
-    if not isinstance(config, ClassifierEnsembleConfig):
+    if isinstance(config, RegressorEnsembleConfig):
+        if config.target_transform is not None:  # fitted here, read back at predict to move the borders (:531-538)
+            y_train = config.target_transform.fit_transform(y_train.reshape(-1, 1)).ravel()
+    elif isinstance(config, ClassifierEnsembleConfig):
+        if config.class_permutation is not None:
+            y_train = config.class_permutation[y_train]
+    else:
         raise ValueError(f"Invalid ensemble config type: {type(config)}")
-    if config.class_permutation is not None:
-        y_train = config.class_permutation[y_train]
     if X_train is None:
         return config, None, None, y_train, None
     static_seed, _ = infer_random_state(random_state)

@@ -238,8 +238,8 @@ def load_model_criterion_config(
     """``utils.py:271-369`` without the download branch (no network: a missing file raises)."""
     from multimodalpfn_amd.model.loading import load_model
 
-    if which != "classifier" or check_bar_distribution_criterion:
-        raise NotImplementedError("only the classifier checkpoint family is served")
+    if which not in ("classifier", "regressor"):
+        raise ValueError(f"Invalid which: {which}")
     if model_path is None:
         # "auto": the cached file name of the reference (TABPFN_MODEL_CACHE_DIR, else the user cache dir)
         cache = os.environ.get("TABPFN_MODEL_CACHE_DIR", "").strip()
@@ -261,4 +261,70 @@ def load_model_criterion_config(
         features_per_group=features_per_group,
     )
     model.cache_trainset_representation = cache_trainset_representation
+    if check_bar_distribution_criterion:  # utils.py:360-368
+        from multimodalpfn_amd.bar_distribution import FullSupportBarDistribution
+
+        if not isinstance(criterion, FullSupportBarDistribution):
+            raise ValueError(f"The model loaded, '{model_path}', was expected to have a FullSupportBarDistribution "
+                             f"criterion, but instead  had a {type(criterion).__name__} criterion.")
     return model, criterion, config
+
+
+# ---- regression: a member's borders after its target transform (utils.py:42-95,748-795) ------------------------
+
+
+def _repair_borders(borders: np.ndarray, *, inplace: Literal[True]) -> None:
+    """``utils.py:42-65``: NaN borders at the upper end collapse onto the largest finite one and the last border is
+    doubled; a last bucket narrower than 1e-6 is widened by a tenth of its border, an empty first one likewise."""
+    if inplace is not True:
+        raise NotImplementedError("Only inplace is supported")
+    if np.isnan(borders[-1]):
+        nans = np.isnan(borders)
+        borders[nans] = borders[~nans].max()
+        borders[-1] = borders[-1] * 2
+    if borders[-1] - borders[-2] < 1e-6:
+        borders[-1] = borders[-1] * 1.1
+    if borders[0] == borders[1]:
+        borders[0] -= np.abs(borders[0] * 0.1)
+
+
+def _cancel_nan_borders(*, borders: np.ndarray, broken_mask: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+    """``utils.py:68-95``: broken borders must form one run from either end.  Each run collapses onto its first
+    sound neighbour, the outermost border is set one unit beyond, and every bar that touches a broken border is
+    cancelled (its logit is set to -inf at predict)."""
+    borders = borders.copy()
+    falls = (broken_mask[:-1] > broken_mask[1:]).sum()  # a broken run ending: one from the left end at most
+    rises = (broken_mask[1:] > broken_mask[:-1]).sum()  # a broken run starting: one to the right end at most
+    assert rises <= 1
+    assert falls <= 1
+    if falls:
+        assert bool(broken_mask[0]) is True
+        first_sound = np.where(broken_mask[:-1] > broken_mask[1:])[0][0] + 1
+        borders[:first_sound] = borders[first_sound]
+        borders[0] = borders[1] - 1.0
+    if rises:
+        assert bool(broken_mask[-1]) is True
+        last_sound = np.where(broken_mask[1:] > broken_mask[:-1])[0][0]
+        borders[last_sound + 1:] = borders[last_sound]
+        borders[-1] = borders[-2] + 1.0
+    return borders, broken_mask[1:] | broken_mask[:-1]
+
+
+def _transform_borders_one(borders: np.ndarray, target_transform, *, repair_nan_borders_after_transform: bool):
+    """``utils.py:748-794``: the criterion's borders through the inverse of a member's fitted target transform.
+    Returns (cancel mask over the bars or None, whether the result came out descending, the borders ascending)."""
+    from multimodalpfn_amd.constants import REGRESSION_NAN_BORDER_LIMIT_LOWER, REGRESSION_NAN_BORDER_LIMIT_UPPER
+
+    borders_t = target_transform.inverse_transform(borders.reshape(-1, 1)).squeeze()
+    cancel = None
+    if repair_nan_borders_after_transform:
+        broken = (~np.isfinite(borders_t) | (borders_t > REGRESSION_NAN_BORDER_LIMIT_UPPER)
+                  | (borders_t < REGRESSION_NAN_BORDER_LIMIT_LOWER))
+        if broken.any():
+            borders_t, cancel = _cancel_nan_borders(borders=borders_t, broken_mask=broken)
+    _repair_borders(borders_t, inplace=True)
+    descending = (np.argsort(borders_t) == np.arange(len(borders_t) - 1, -1, -1)).all()
+    if descending:
+        borders_t = borders_t[::-1]
+        cancel = cancel[::-1] if cancel is not None else None
+    return cancel, descending, borders_t
