@@ -84,6 +84,18 @@ int mmpfn_text_forward(mmpfn_enc* enc, const int32_t* ids, const int32_t* mask, 
 int mmpfn_enc_attention(mmpfn_enc* enc, const void* qkv, const float* kbias, void* out, int B, int L, int H,
                         int precision);
 
+/* Kernel tap (tests, diagnostics): the towers' bf16 GEMM (256 x 256 tiles) on device buffers:
+ * C [M][N] = epilogue(A [M][K] . W [N][K]^T + bias), A and W bf16, bias [N] fp32 or NULL, C rows N apart.
+ * epi selects the epilogue; act (MMPFN_ENC_EPI_BF16 only): 0 none, 1 GELU (tanh form).  gamma [N] fp32 or NULL
+ * (1) is read by MMPFN_ENC_EPI_RESID alone.  N % 256 != 0, K % 32 != 0, K <= 0, an unknown epi, or act with an
+ * fp32 epilogue -> MMPFN_ERR_INVALID.  Rows >= M of C are not written.  Runs on the encoder's stream; needs no
+ * model. */
+#define MMPFN_ENC_EPI_BF16 0  /* C bf16 = act(acc + bias) */
+#define MMPFN_ENC_EPI_RESID 1 /* C fp32 += gamma * (acc + bias) */
+#define MMPFN_ENC_EPI_F32 2   /* C fp32 = acc + bias */
+int mmpfn_enc_linear(mmpfn_enc* enc, const void* A, const void* W, const float* bias, const float* gamma, void* C,
+                     int M, int N, int K, int epi, int act);
+
 #ifdef __cplusplus
 }
 #endif

@@ -171,7 +171,9 @@ MODALITY_SIGNATURES = [
     ("mmpfn_vit_forward", _i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i]),
     ("mmpfn_text_forward", _i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i]),
     ("mmpfn_enc_attention", _i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i]),
+    ("mmpfn_enc_linear", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
 ]
+MMPFN_ENC_EPI_BF16, MMPFN_ENC_EPI_RESID, MMPFN_ENC_EPI_F32 = 0, 1, 2  # mmpfn_enc_linear's epilogues
 
 _LIB = None
 

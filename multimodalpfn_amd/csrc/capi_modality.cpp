@@ -421,6 +421,24 @@ int mmpfn_enc_attention(mmpfn_enc* enc, const void* qkv, const float* kbias, voi
   return MMPFN_OK;
 }
 
+static_assert(MMPFN_ENC_EPI_BF16 == GT_BF16 && MMPFN_ENC_EPI_RESID == GT_RESID && MMPFN_ENC_EPI_F32 == GT_F32,
+              "the header's epilogue codes are launch_gemm_tile's");
+
+int mmpfn_enc_linear(mmpfn_enc* enc, const void* A, const void* W, const float* bias, const float* gamma, void* C,
+                     int M, int N, int K, int epi, int act) {
+  if (!enc) return MMPFN_ERR_INVALID;
+  if (!A || !W || !C || M <= 0 || N <= 0) return fail(enc, MMPFN_ERR_INVALID, "A, W, C and M, N > 0");
+  HIPCHK(hipSetDevice(enc->device));
+  // the launcher is the one check of the shape and the epilogue: what it refuses launches nothing
+  const hipError_t e = launch_gemm_tile(A, W, bias, gamma, C, N, M, N, K, epi, act, enc->stream);
+  if (e == hipErrorInvalidValue)
+    return fail(enc, MMPFN_ERR_INVALID,
+                "mmpfn_enc_linear needs N % 256 == 0, K % 32 == 0, K > 0, epi one of MMPFN_ENC_EPI_*, and act 0 "
+                "with an fp32 epilogue (act 0 or 1 with MMPFN_ENC_EPI_BF16)");
+  HIPCHK(e);
+  return MMPFN_OK;
+}
+
 int mmpfn_text_forward(mmpfn_enc* enc, const int32_t* ids, const int32_t* mask, const int32_t* types, int B, int L,
                        float* cls, float* hidden, int precision) {
   if (!enc) return MMPFN_ERR_INVALID;

@@ -14,7 +14,7 @@ enum GtEpi : int {
 };
 
 // bf16 C = A[M][K] . W[N][K]^T on 256 x 256 tiles; N % 256 == 0, K % 32 == 0, A rows K apart;
-// act (GT_BF16 only): 0 none, 1 GELU (erf)
+// act (GT_BF16 only): 0 none, 1 GELU (tanh form, common.h gelu_tanh_fast)
 hipError_t launch_gemm_tile(const void* A, const void* W, const float* bias, const float* gamma, void* C,
                             int64_t ldc, int M, int N, int K, int epi, int act, hipStream_t st);
 
