@@ -36,6 +36,9 @@
  *   mmpfn_feature_attention / mmpfn_item_attention_block / mmpfn_mlp_ln
  *       <- model/layer.py:332-339 / :341-379 / :410-424 with the post-norms :437-455
  *          (one PerFeatureEncoderLayer sublayer each)
+ *   mmpfn_outproj_mlp_ln
+ *       <- model/layer.py:341-379's out-projection with its post-norm, then :410-424 with its own (:437-455):
+ *          what follows the item attention's softmax(QK^T)V in one PerFeatureEncoderLayer
  *   mmpfn_mgm / mmpfn_cap
  *       <- model/transformer.py:33-57 MultiheadGatedMLP / :60-88 CrossAttentionPooler
  */
@@ -281,13 +284,30 @@ int mmpfn_kernel_timing_read(mmpfn_ctx* ctx, double* total_ms, int64_t* launches
 int mmpfn_set_parity_attention_min_keys(int n, int form);
 
 /* Per-sublayer taps: one sublayer of layer `layer` on a caller-provided state, in place, on the
- * context stream (the forward itself fuses across these seams: the bf16 item-attention
- * out-projection runs inside the MLP kernel there).  X: device [T][S][E] fp32, the engine's
+ * context stream (the forward itself fuses across these seams: the 16-bit modes' item-attention
+ * out-projection runs inside the MLP kernel there -- mmpfn_outproj_mlp_ln below is the tap on that).  X: device [T][S][E] fp32, the engine's
  * token-major state of ONE member (reference order [S][T][E] transposed).  `rows` = S * T. */
 int mmpfn_feature_attention(mmpfn_ctx* ctx, int layer, float* X, int S, int T, int precision);
 /* train rows [0, N) attend their own heads, rows [N, S) head 0's K/V (MQA) */
 int mmpfn_item_attention_block(mmpfn_ctx* ctx, int layer, float* X, int S, int T, int N, int precision);
 int mmpfn_mlp_ln(mmpfn_ctx* ctx, int layer, float* X, int64_t rows, int precision);
+/* The step behind the item attention as the forwards run it, attention output -> state:
+ *   X <- LN(X' + MLP_layer(X')),  X' = LN(X + O . Wout_layer^T)
+ * X [rows][E] fp32, in place (MMPFN_PREC_F16: through an fp16 copy, as the other taps).  O [rows][E] is the item
+ * attention's output, O[row][32 h + d] of head h, in the mode's attention-output element type, taken as it is (the
+ * convention of mmpfn_item_attention_layer_ex): fp32 for MMPFN_PREC_F32 / _F32_MFMA, bf16 for MMPFN_PREC_BF16*, fp16
+ * for MMPFN_PREC_F16*.  Row-wise: any row count >= 1, no token limit.
+ * Which kernels the three row-wise taps run, by mode:
+ *   mmpfn_outproj_mlp_ln        16-bit: mlp_rows_kernel with the out-projection prologue (RES), one launch -- the
+ *                               kernel of every 16-bit forward; fp32: the out-projection + LN kernel, then the MLP
+ *                               kernel -- the forwards' two launches.  The forwards and this tap share one host function.
+ *   mmpfn_item_attention_block  16-bit: its out-projection runs the stand-alone rowgemm kernel (launch_rowgemm_resln),
+ *                               which no 16-bit forward launches; fp32: the forwards' kernels.
+ *   mmpfn_mlp_ln                16-bit: mlp_rows_kernel without the prologue (RES = false), which no 16-bit forward
+ *                               launches; fp32: the forwards' kernel.
+ * MMPFN_ERR_INVALID (mmpfn_last_error says which) for rows <= 0, a null O, a layer outside [0, nlayers) or an
+ * unknown precision; nothing is launched then. */
+int mmpfn_outproj_mlp_ln(mmpfn_ctx* ctx, int layer, float* X, const void* O, int64_t rows, int precision);
 /* modality heads: image [S][n_mod][nhid] -> MGM tokens [S][mgm*n_mod][E] (head-major, as the
  * reference concatenates them); MGM tokens [S][M][E] -> CAP tokens [S][cap][E] */
 int mmpfn_mgm(mmpfn_ctx* ctx, const float* image, int S, int n_mod, float* tokens, int precision);

@@ -517,8 +517,9 @@ int feat_sublayer(mmpfn_ctx* ctx, const LayerW& L, void* Xv, int S, int T, int M
 
 // ---- attention between items (layer.py:341-379) of layer l; rows of all members: logical row
 //      (member*T + t)*N + n -> memory row (member*T + t)*S + n, attention batch member*T + t.
-//      fuse_out: the out-projection + residual + LN is left to the MLP kernel's prologue (the
-//      attention output stays in ws_O); otherwise X <- LN(X + O Wout^T) here.
+//      fuse_out: the out-projection + residual + LN is left to the caller's layer_tail (the attention output
+//      stays in ws_O; the 16-bit modes run it as the MLP kernel's prologue); otherwise -- the
+//      mmpfn_item_attention_block tap -- X <- LN(X + O Wout^T) here.
 //      last: the pruned form of a forward's last layer (last_layer_tail): the target-token column T-1 of every
 //      member only -- M columns, T*S rows apart, into compact Q / K / V^T scratch and a compact O [M][S][E] -- and
 //      of its queries only the test rows; the out-projection is left to the caller.  The test rows keep the places
@@ -618,15 +619,25 @@ int mlp_sublayer(mmpfn_ctx* ctx, const LayerW& L, void* Xv, int64_t RM, PrecMode
   return MMPFN_OK;
 }
 
+// ---- attention output -> state, the step behind the item attention: X <- LN(X' + MLP(X')), X' = LN(X + O Wout^T)
+//      over `rows` tokens.  O: the item attention's output in the mode's type (PrecMode::attn_out; fp32 in the fp32
+//      modes).  The 16-bit modes run it as one kernel (the out-projection is the MLP kernel's prologue), the fp32 modes
+//      as two.  run_layer, last_layer_tail and the mmpfn_outproj_mlp_ln tap all come here: what the tap runs is what
+//      the forwards run.
+int layer_tail(mmpfn_ctx* ctx, const LayerW& L, void* X, const void* O, int64_t rows, PrecMode pm) {
+  if (pm.is16()) return mlp_sublayer(ctx, L, X, rows, pm, O);
+  RC(out_proj_ln(ctx, pm, true, L.item_out, O, X, rows));
+  return mlp_sublayer(ctx, L, X, rows, pm, nullptr);
+}
+
 int run_layer(mmpfn_ctx* ctx, int l) {
   const LayerW& L = ctx->w.layers[l];
   const int S = ctx->S, T = ctx->T, N = ctx->N, Npad = ctx->Npad, M = ctx->M;
   const PrecMode pm = lane_prec(*ctx);
   void* Xall = ctx->ws_X.p;
-  const bool fuse = pm.is16();  // the 16-bit MLP kernel runs the item-attention out-projection as its prologue
   RC(feat_sublayer(ctx, L, Xall, S, T, M, pm));
-  RC(item_sublayer(ctx, l, Xall, S, T, N, Npad, M, pm, fuse));
-  return mlp_sublayer(ctx, L, Xall, (int64_t)S * T * M, pm, fuse ? ctx->ws_O.p : nullptr);
+  RC(item_sublayer(ctx, l, Xall, S, T, N, Npad, M, pm, true));  // the attention output stays in ws_O
+  return layer_tail(ctx, L, Xall, ctx->ws_O.p, (int64_t)S * T * M, pm);
 }
 
 // The last layer of a forward, pruned to what the decoder reads: the test rows [N, S) of the target token (column
@@ -642,17 +653,15 @@ int last_layer_tail(mmpfn_ctx* ctx, int l) {
   const LayerW& L = ctx->w.layers[l];
   const int S = ctx->S, T = ctx->T, N = ctx->N, Npad = ctx->Npad, M = ctx->M, E = ctx->d.emsize;
   const PrecMode pm = lane_prec(*ctx);
-  const bool fuse = pm.is16();
   RC(feat_sublayer(ctx, L, ctx->ws_X.p, S, T, M, pm, true));
-  RC(item_sublayer(ctx, l, ctx->ws_X.p, S, T, N, Npad, M, pm, fuse, true));
+  RC(item_sublayer(ctx, l, ctx->ws_X.p, S, T, N, Npad, M, pm, true, true));
   const int64_t Q = S - N;
   if (Q == 0) return MMPFN_OK;
-  const size_t ob = fuse ? 2 : 4;  // the attention output's element: 16-bit in the 16-bit modes
+  const size_t ob = pm.op_bytes();  // the attention output's element: 16-bit in the 16-bit modes
   for (int m = 0; m < M; ++m) {
     void* X = (char*)ctx->ws_X.p + (((size_t)m * T + T - 1) * S + N) * E * pm.state_bytes();
     const void* O = (const char*)ctx->ws_O.p + ((size_t)m * S + N) * E * ob;  // compact: one column per member
-    if (!fuse) RC(out_proj_ln(ctx, pm, true, L.item_out, O, X, Q));
-    RC(mlp_sublayer(ctx, L, X, Q, pm, fuse ? O : nullptr));
+    RC(layer_tail(ctx, L, X, O, Q, pm));
   }
   return MMPFN_OK;
 }
@@ -1314,6 +1323,16 @@ int mmpfn_mlp_ln(mmpfn_ctx* ctx, int layer, float* X, int64_t rows, int precisio
   const PrecMode pm = decode_prec(precision, -1);  // row-wise: no token limit
   return state_tap(ctx, X, rows * ctx->d.emsize, pm, [&](void* Xs) {
     return mlp_sublayer(ctx, ctx->w.layers[layer], Xs, rows, pm, nullptr);
+  });
+}
+
+int mmpfn_outproj_mlp_ln(mmpfn_ctx* ctx, int layer, float* X, const void* O, int64_t rows, int precision) {
+  RC(tap_check(ctx, layer, X, precision));
+  if (rows <= 0) return fail(ctx, MMPFN_ERR_INVALID, "bad row count");
+  if (!O) return fail(ctx, MMPFN_ERR_INVALID, "null attention output");
+  const PrecMode pm = decode_prec(precision, -1);  // row-wise: no token limit
+  return state_tap(ctx, X, rows * ctx->d.emsize, pm, [&](void* Xs) {
+    return layer_tail(ctx, ctx->w.layers[layer], Xs, O, rows, pm);
   });
 }
 

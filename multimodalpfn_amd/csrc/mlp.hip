@@ -2,10 +2,11 @@
 //   X <- LayerNorm(X + GELU(X W1^T) W2^T)          (mlp.py:93-104, layer.py:437-455)
 //
 // One 256-thread block owns 64 rows.  The row tile of X is converted once into LDS;
-// the 768-wide hidden layer is produced in four 192-column chunks, each GELU'd into
-// an LDS tile and immediately contracted with the matching 192-column slice of W2,
-// so the [rows, 768] hidden activations never touch HBM (the unfused pair moved
-// 2 x 127 MB per layer at the PAD-UFES shape).  Weights stream from L2 in 128-byte
+// the hidden layer (Fh wide, any multiple of 192: four chunks at the checkpoints' 768,
+// one to five in tests/test_layer_tail_gpu.py) is produced in Fh / 192 chunks of 192
+// columns, each GELU'd into an LDS tile and immediately contracted with the matching
+// 192-column slice of W2, so the [rows, Fh] hidden activations never touch HBM (the
+// unfused pair moved 2 x 127 MB per layer at the PAD-UFES shape).  Weights stream from L2 in 128-byte
 // K slices (64 bf16 / 32 f32) with the next slice's loads in flight during the
 // current slice's MFMAs.  bf16: v_mfma_f32_16x16x32_bf16; f32 (parity):
 // v_mfma_f32_16x16x4_f32.  Residual + LayerNorm(no affine) in the epilogue.

@@ -603,6 +603,23 @@ class HipEngine:
                     "mmpfn_mlp_ln")
         return Xd
 
+    def outproj_mlp_ln(self, layer: int, X: torch.Tensor, O: torch.Tensor, precision: int) -> torch.Tensor:
+        """``LN(X' + MLP_layer(X'))`` with ``X' = LN(X + O Wout_layer^T)`` through ``mmpfn_outproj_mlp_ln``: the
+        step behind the item attention on the forwards' own kernels (the 16-bit modes: one launch).  ``O`` ``[rows, E]``,
+        the attention output, is converted to the mode's type (fp32 / bf16 / fp16); returns fp32 ``[rows, E]``."""
+        odt = (torch.float32 if precision in (_lib.PREC_F32, _lib.PREC_F32_MFMA)
+               else torch.float16 if precision in (_lib.PREC_F16, _lib.PREC_F16_F8, _lib.PREC_F16_F8E5)
+               else torch.bfloat16)
+        Xd = self._dev(X).contiguous().clone()
+        Od = self._dev(O, odt)
+        rows = Xd.numel() // self.cfg.emsize
+        if Od.numel() != Xd.numel():
+            raise ValueError(f"O has {Od.numel()} elements, X {Xd.numel()}")
+        self._bind_stream()
+        self._check(self.lib.mmpfn_outproj_mlp_ln(self.ctx, layer, _ptr(Xd), _ptr(Od), rows, precision),
+                    "mmpfn_outproj_mlp_ln")
+        return Xd
+
     def mgm(self, image, precision: int) -> torch.Tensor:
         """MultiheadGatedMLP tokens ``[S, mgm * n_mod, E]`` (transformer.py:33-57)."""
         img = self._dev(image)

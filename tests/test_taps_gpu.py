@@ -6,6 +6,16 @@ fp32 parity mode (prec 0: split-bf16 three-product MFMAs) <= 5e-5 relative to ma
 sublayer (the oracle runs fp64); fp32-input MFMA mode (prec 2) <= 2e-5; bf16 mode <= 2e-2 (bf16
 operands, fp32 accumulation / LayerNorm); fp16 mode (prec 5: fp16 state and operands, the item
 attention's P.V on bf16) <= 1e-2.
+
+Which kernels a layer tap runs.  In the fp32 modes (0, 2) every tap runs the forwards' kernels.  In the 16-bit modes
+(1, 5) the forwards fuse the item attention's out-projection + LayerNorm into the MLP kernel as its prologue
+(``mlp_rows_kernel<2, RES = true>``), so of the three taps here
+  ``mmpfn_feature_attention``     runs the forwards' ``feat_rows_kernel`` (T <= 64);
+  ``mmpfn_item_attention_block``  runs the forwards' q|k|v projection and attention, but its out-projection on
+                                  ``launch_rowgemm_resln``, which no 16-bit forward launches;
+  ``mmpfn_mlp_ln``                runs ``mlp_rows_kernel<2, RES = false>``, which no 16-bit forward launches either.
+The forwards' own kernel is behind a fourth tap, ``mmpfn_outproj_mlp_ln``, tested alone in
+tests/test_layer_tail_gpu.py.
 """
 
 import pytest
