@@ -20,10 +20,15 @@
 // The softmax scale log2(e)/sqrt(32) is folded into Wq (exp2 on the scores).
 // Only the weights move: they are stored as LDS images (capi.cpp pack_feat_rows: 416-B rows,
 // so conflict-free ds_read_b128) and copied global -> LDS by LDS-DMA (global_load_lds, 1 KB
-// per wave-instruction, no staging registers): per head a 39 KB QKV slice, double buffered,
-// the next head's in flight during the current head; the 78 KB out-projection image over both
-// buffers at the end.  80 KB of LDS and <= 256 VGPRs per 4-row block: two blocks per CU.
-// Per row: 6*(18*NT + NT^2 + 2*NT*ceil(NT/2)) + 72*NT MFMAs; HBM traffic = X read + written once.
+// per wave-instruction, no staging registers) in groups of 32 rows (13 KB: a head's Q, K or V rows, a sixth of the
+// out-projection image) through a ring of 13-KB slots.  Six slots (78 KB) where nothing else needs LDS: the next
+// head's Q | K | V in flight during the current head, one barrier per head, the 78 KB out-projection image whole at
+// the end.  The three-tile full form, the one short of registers, keeps the last tile's finished O^T fragments in
+// LDS (24 KB) instead, beside a three-slot ring (39 KB) handed on twice per head and once per out-projection group.
+// The out-projection runs two token tiles per Wout fragment read.  <= 79872 B of LDS and <= 256 VGPRs per 4-row
+// block, no scratch: two blocks per CU (NT = 4: one wave per SIMD).  Resources (VGPRs, LDS): NT = 3 full form 246 /
+// 250 (fp16 / bf16), 64512 B; its last-layer form 184 / 182, 79872 B; tests/test_featrow_nospill_codegen.py.
+// Per row: 6*(18*NT + NT^2 + 2*NT*ceil(NT/2)) + 72*NT MFMAs; HBM traffic = X read + written once (measured 0.99x).
 //
 // F16 (PREC_F16: the state X is fp16, the reference's autocast dtype): the row's X^T fragments are
 // loaded as they are stored (16-B loads, no conversion) and are the exact residual, so X is read once;
@@ -42,8 +47,23 @@ namespace {
 constexpr int FR_E = 192;                        // model width
 constexpr int FR_H = 6;                          // heads
 constexpr int FR_ST = FEAT_IMG_STRIDE;           // bf16 row stride of every LDS image (416 B)
-constexpr int FR_QKV_IMG = 96 * FR_ST;           // one head's QKV image: 19968 bf16 = 39 KB
-constexpr int FR_PIECES = FR_QKV_IMG * 2 / 1024; // 1-KB DMA pieces per QKV image (39)
+constexpr int FR_GRP = 32 * FR_ST;               // one image group = one ring slot: 32 rows, 6656 bf16 = 13 KB
+constexpr int FR_GPIECES = FR_GRP * 2 / 1024;    // 1-KB DMA pieces per group (13)
+constexpr int FR_QKV_GRPS = 3 * FR_H;            // groups 0 .. 17: head h's Q | K | V at 3 h + {0, 1, 2}; then Wout's
+constexpr int FR_FRAG = 512;                     // one parked fragment of a wave: 64 lanes x 16 B (in bf16 elements)
+
+// Where the finished O^T fragment of (head h, query tile t) waits for the out-projection: a parking place in LDS
+// (the wave's own, lane-linear: each lane writes and later reads back its own 16 B, no conflicts), or -1 = in
+// registers.  Only the three-tile full form is short of registers (two waves per SIMD: 256): it spilled 32 (fp16) /
+// 16 (bf16) of them to scratch, which reached HBM.  Its tile 2 runs alone in the out-projection's second pass, so
+// tile 2's six fragments are parked: the fewest that leave no spill in either form (parking tiles 0 and 1 of the
+// first one or two heads as well measured the same, profiles/r08/INDEX.md).
+template <int NT, bool LAST>
+constexpr int fr_park(int h, int t) {
+  return NT == 3 && !LAST && t == 2 ? h : -1;
+}
+template <int NT, bool LAST>
+constexpr int FR_NPARK = NT == 3 && !LAST ? FR_H : 0;
 
 template <typename X8>
 __device__ __forceinline__ X8 cat8(const f32x4& a, const f32x4& b, float s = 1.0f) {
@@ -81,9 +101,15 @@ __global__ __launch_bounds__(256, NT <= 3 ? 2 : 1) void feat_rows_kernel(void* _
   typedef std::conditional_t<F16, f16, float> XT;  // state element
   typedef typename Op16<F16>::t WT;
   const WT* __restrict__ pack = (const WT*)packv;
-  __shared__ __attribute__((aligned(1024))) WT wbuf[2 * FR_QKV_IMG];
+  constexpr int NPARK = FR_NPARK<NT, LAST>;
+  // The weight images move through a ring of 13-KB slots, item i (image group i; the out-projection's groups again
+  // for a second pass of the short ring) in slot i % NSLOT.  Six slots hold two heads' Q | K | V, or the whole
+  // out-projection image: one barrier per head, as two 39-KB buffers.  The form that parks fragments has room for
+  // three slots only and hands them on twice per head and once per out-projection group (below).
+  constexpr int NSLOT = NPARK ? 3 : 6;
+  __shared__ __attribute__((aligned(1024))) WT wbuf[NSLOT * FR_GRP + 4 * NPARK * FR_FRAG];  // ring | parking
   // (wave in an SGPR: the LDS-DMA piece addresses below are then a scalar base + the lane's 16-B offset, the
-  // saddr form, instead of one 64-bit VGPR address per piece -- 10 pieces a head, ~19 VGPRs at the peak)
+  // saddr form, instead of one 64-bit VGPR address per piece -- ~19 VGPRs at the peak)
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int n = lane & 15, g = lane >> 4;
   const int row = blockIdx.x * 4 + wave;  // row over the batch: member row / S, table row row % S
@@ -93,34 +119,65 @@ __global__ __launch_bounds__(256, NT <= 3 ? 2 : 1) void feat_rows_kernel(void* _
   const int64_t SE = (int64_t)S * FR_E;
   XT* __restrict__ X = (XT*)Xv + (int64_t)mem * T * SE;
 
-  // LDS-DMA of `pieces` KB from src (global) to dst (LDS), KB piece p by wave p % 4
+  // LDS-DMA of image group grp (13 KB of the pack) into its ring slot, KB piece p by wave p % 4
   // (non-dependent pointer types: a builtin call on a template-dependent type is checked at instantiation,
   // where the host pass cannot resolve it, and the kernel's host stub is then silently dropped)
   const uint32_t dvoff = lane * 16;
-  // the asm DMA issues are invisible to the compiler's waitcnt pass: each barrier that publishes an image waits
-  // for this wave's pieces itself (vmcnt counts them with the wave's other global loads)
-  auto dma_wait = []() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); };
   auto lds_u32 = [](const void* p) { return (unsigned)(uintptr_t)(lds_void*)p; };
-  auto dma = [&](const void* srcv, void* dstv, int pieces) {
-    const char* src = (const char*)srcv;
-    const unsigned dst = lds_u32(dstv);
-    for (int p = wave; p < pieces; p += 4)
-      fr_dma16(dvoff, src + p * 1024, __builtin_amdgcn_readfirstlane(dst + p * 1024));
+  auto dma_piece = [&](int item, int p) {
+    const int grp = item < FR_QKV_GRPS + 6 ? item : item - 6;  // (the short ring's second pass over Wout)
+    const char* src = (const char*)(pack + grp * FR_GRP);
+    const unsigned dst = lds_u32(wbuf + (item % NSLOT) * FR_GRP);
+    fr_dma16(dvoff, src + p * 1024, __builtin_amdgcn_readfirstlane(dst + p * 1024));
   };
-
-  // the same copy one piece at a time: piece i of this wave (wave + 4 i), clamped to the last piece so that
-  // the call is branch-free (a clamped piece rewrites the last piece's bytes with the same data)
-  auto dma_piece = [&](const void* srcv, void* dstv, int i) {
-    const int p = min(wave + 4 * i, FR_PIECES - 1);
-    fr_dma16(dvoff, (const char*)srcv + p * 1024, __builtin_amdgcn_readfirstlane(lds_u32(dstv) + p * 1024));
+  // three slots: a group's 13 pieces are three per wave (dma_part i = 0 .. 2, branch-free) and the 13th by wave 0
+  // (dma_tail)
+  auto dma_part = [&](int item, int i) { dma_piece(item, wave + 4 * i); };
+  auto dma_tail = [&](int item) {
+    if (wave == 0) dma_piece(item, FR_GPIECES - 1);
   };
+  auto dma_grp = [&](int item) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) dma_part(item, i);
+    dma_tail(item);
+  };
+  // Six slots: three consecutive items (a head's Q | K | V, a half of Wout) are one 39-KB image in three consecutive
+  // slots and move as the double buffer moved them: 39 pieces, ten per wave (dma_img_part i = 0 .. 9, clamped to the
+  // last piece so that the call is branch-free: a clamped piece rewrites the last piece's bytes with the same data)
+  // (dma_img leaves the address arithmetic to dma_piece: with the two bases hoisted out of its loop by hand the fp16
+  // four-tile form came out with its O^T array in scratch, 400 B per lane; tests/test_featrow_nospill_codegen.py)
+  auto dma_img = [&](int item0) {
+    for (int p = wave; p < 3 * FR_GPIECES; p += 4) dma_piece(item0, p);
+  };
+  auto dma_img_part = [&](int item0, int i) { dma_piece(item0, min(wave + 4 * i, 3 * FR_GPIECES - 1)); };
+  // SPREAD: an item's dma_part issues go one per k-step into the projection phase that follows its barrier instead of
+  // all at the barrier (an LDS-DMA's issue cost grows with the other issues of its phase, MI355X_MICROARCH.md; the
+  // fp16 form: 102.8 against 106.7 us when measured, profiles/r04/ab_feat_rows_dma_spread.txt; the bf16 form, not
+  // measured with it, issues at the barrier)
 #ifndef FR_DMA_SPREAD
 #define FR_DMA_SPREAD 1
 #endif
-  constexpr int FR_PPW = (FR_PIECES + 3) / 4;  // pieces per wave (10)
-  constexpr bool SPREAD = FR_DMA_SPREAD && F16;  // the bf16 form: +16 spilled registers, not spread
+  constexpr bool SPREAD = FR_DMA_SPREAD && F16;
+  auto dma_start = [&](int item) {  // at the barrier: the whole item, or its tail with the parts to follow
+    if constexpr (SPREAD) dma_tail(item);
+    else dma_grp(item);
+  };
+  // The asm DMA issues are invisible to the compiler's waitcnt pass, so each barrier that publishes a group waits
+  // for this wave's pieces itself (vmcnt counts them with the wave's other global accesses; loads return in order).
+  // sync_all: everything this wave issued has landed.  sync_but_last: everything but the group issued last -- at
+  // most 3 accesses stay outstanding, the youngest group's (wave 0, with four pieces, waits for one of them too; a
+  // younger store or load only makes the wait longer).  Both also retire the wave's LDS reads of the slot that the
+  // next DMA overwrites.  This is the counted-vmcnt idiom of LDS-DMA rings: an LDS-DMA is a load on the VM counter,
+  // loads retire in issue order, so vmcnt(N) with N = the pieces of the groups left in flight means every older
+  // group has landed; a reader may touch it only after a barrier that follows that wait.
+  auto sync_all = []() {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+  };
+  auto sync_but_last = []() { asm volatile("s_waitcnt vmcnt(3) lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
 
-  dma(pack, wbuf, FR_PIECES);  // head 0 -> buffer 0
+  if constexpr (NSLOT == 6) dma_img(0);  // head 0's Q | K | V
+  else dma_grp(0), dma_grp(1), dma_grp(2);
   // row addresses: a wave-uniform row base and a 32-bit lane offset per token tile (the saddr form: one VGPR per
   // tile where a 64-bit address per tile, live to the final stores, cost spills); lane offset = token t, features 8 g
   const char* const xrow = (const char*)(X + (int64_t)sr * FR_E);
@@ -149,22 +206,23 @@ __global__ __launch_bounds__(256, NT <= 3 ? 2 : 1) void feat_rows_kernel(void* _
       }
     }
   }
-  dma_wait();
-  __syncthreads();
+  sync_all();
+  if constexpr (NSLOT == 6 && !SPREAD) dma_img(3);  // head 1's, in flight during head 0
 
-  X8 of[FR_H][NT - Q0];  // O^T fragments of every head (K-step h of the out-projection), query tiles Q0 ..
+  constexpr int NTQ = NT - Q0;  // query tiles
+  // the wave's parking places (fragment s at + s FR_FRAG) and the fragments that stay in registers
+  WT* const park = wbuf + 3 * FR_GRP + wave * (NPARK * FR_FRAG) + lane * 8;
+  X8 of[FR_H][NTQ];  // O^T fragments of every head (K-step h of the out-projection), query tiles Q0 ..
 #pragma unroll
   for (int h = 0; h < FR_H; ++h) {
-    // the next image: head h+1's QKV, or after the last head the out-projection image's first half (buffer 0
-    // is free); FR_DMA_SPREAD issues it one piece per k-step of the projections below instead of as one burst
-    // at the head's start (an LDS-DMA's issue cost grows with the other issues of its phase,
-    // MI355X_MICROARCH.md); the end-of-head barrier retires it either way
-    const WT* nsrc = h + 1 < FR_H ? pack + (h + 1) * FR_QKV_IMG : pack + FR_H * FR_QKV_IMG;
-    WT* ndst = h + 1 < FR_H ? wbuf + ((h + 1) & 1) * FR_QKV_IMG : wbuf;
-    if constexpr (!SPREAD) dma(nsrc, ndst, FR_PIECES);
-    const WT* wq = wbuf + (h & 1) * FR_QKV_IMG;  // [96][FR_ST]: Q (permuted) | K (permuted) | V
-
+    // Items 3 h + {0, 1, 2} are this head's Q, K, V rows, [32][FR_ST] each, read in that order; items 18 .. are
+    // the out-projection image's groups.  Six slots: the end-of-head barrier publishes the next head's three items
+    // and frees this head's slots for the items of the head after the next.  Three slots: two barriers per head
+    // hand them on -- after the K phase slots 0 and 1 take the next head's Q and K (they land during the V phase
+    // and the attention; the end-of-head barrier publishes them), after the head slot 2 takes the next head's V
+    // (it lands during the next head's Q and K phases, whose barrier publishes it).
     // ---- Q^T, K^T (C^T tiles) of the row, K = 192 in 6 steps (V after, to bound live registers)
+    const WT* wimg = wbuf + ((3 * h) % NSLOT) * FR_GRP;  // [96][FR_ST]: Q (permuted) | K (permuted) | V, a slot each
     X8 qf[NT], kf[NT];
     // Q then K, one set of 2 NT accumulators live at a time (both at once: 54 / 44 spills in the fp16 / bf16
     // forms vs 46 / 24, and 2.5 / 4.5 % slower, profiles/r04/ab_feat_rows_qk_split.txt)
@@ -179,20 +237,26 @@ __global__ __launch_bounds__(256, NT <= 3 ? 2 : 1) void feat_rows_kernel(void* _
       for (int ks = 0; ks < FR_E / 32; ++ks) {
         X8 wqf[2];
 #pragma unroll
-        for (int f = 0; f < 2; ++f) wqf[f] = *(const X8*)(wq + (32 * j + 16 * f + n) * FR_ST + 32 * ks + 8 * g);
+        for (int f = 0; f < 2; ++f) wqf[f] = *(const X8*)(wimg + (32 * j + 16 * f + n) * FR_ST + 32 * ks + 8 * g);
 #pragma unroll
         for (int tt = 0; tt < NT; ++tt) {
           if (j == 0 && tt < Q0) continue;  // (Q of the query tiles only)
 #pragma unroll
           for (int f = 0; f < 2; ++f) qa[f][tt] = mfma16x(wqf[f], xf[tt][ks], qa[f][tt]);
         }
-        if constexpr (SPREAD) {  // pieces 0 .. 9 after the Q and K k-steps 0 .. 4 of each
-          if (ks < FR_PPW / 2) dma_piece(nsrc, ndst, j * (FR_PPW / 2) + ks);
+        if constexpr (SPREAD) {
+          // six slots: the ten parts of the next head's image after the Q and K k-steps 0 .. 4 of each
+          if (NSLOT == 6 && ks < 5) dma_img_part(3 * h + 3, j * 5 + ks);
+          if (NSLOT == 3 && j == 0 && ks < 3 && h > 0) dma_part(3 * h + 2, ks);  // three: this head's V
         }
       }
 #pragma unroll
       for (int tt = 0; tt < NT; ++tt) (j == 0 ? qf[tt] : kf[tt]) = cat8<X8>(qa[0][tt], qa[1][tt]);
       __builtin_amdgcn_sched_barrier(0);
+    }
+    if constexpr (NSLOT == 3) {
+      sync_all();  // this head's V landed; slots 0 and 1 are free
+      dma_start(3 * h + 3), dma_start(3 * h + 4);
     }
     __builtin_amdgcn_sched_barrier(0);  // phases in order: bounds the live registers (2 waves / SIMD)
     // ---- V (C tiles: lane = head dim, 4 consecutive tokens) -> V^T A fragments per key-tile pair
@@ -208,11 +272,12 @@ __global__ __launch_bounds__(256, NT <= 3 ? 2 : 1) void feat_rows_kernel(void* _
       for (int ks = 0; ks < FR_E / 32; ++ks) {
         X8 wvf[2];
 #pragma unroll
-        for (int f = 0; f < 2; ++f) wvf[f] = *(const X8*)(wq + (64 + 16 * f + n) * FR_ST + 32 * ks + 8 * g);
+        for (int f = 0; f < 2; ++f) wvf[f] = *(const X8*)(wimg + (64 + 16 * f + n) * FR_ST + 32 * ks + 8 * g);
 #pragma unroll
         for (int tt = 0; tt < NT; ++tt)
 #pragma unroll
           for (int f = 0; f < 2; ++f) va[f][tt] = mfma16x(xf[tt][ks], wvf[f], va[f][tt]);
+        if constexpr (SPREAD && NSLOT == 3) dma_part(3 * h + 3 + ks / 3, ks % 3);  // the next Q and K (Wout's 0, 1)
       }
 #pragma unroll
       for (int mt = 0; mt < 2; ++mt)
@@ -254,83 +319,122 @@ __global__ __launch_bounds__(256, NT <= 3 ? 2 : 1) void feat_rows_kernel(void* _
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) oa[mt] = mfma16x(vfr[mt][kp], pb, oa[mt]);
       }
-      of[h][qt - Q0] = cat8<X8>(oa[0], oa[1], inv);
+      const int ps = fr_park<NT, LAST>(h, qt);
+      if (ps >= 0) *(X8*)(park + ps * FR_FRAG) = cat8<X8>(oa[0], oa[1], inv);
+      else of[h][qt - Q0] = cat8<X8>(oa[0], oa[1], inv);
       __builtin_amdgcn_sched_barrier(0);
     }
-    dma_wait();  // the next image landed (every wave's pieces: the barrier below); this head's buffer is free
-    __syncthreads();
+    sync_all();  // the next items landed (three slots: all but V's, which goes into slot 2 now)
+    if constexpr (NSLOT == 3) {
+      if (h + 1 < FR_H) dma_start(3 * h + 5);  // the next V: its parts ride in the next head's Q phase
+      else dma_grp(3 * h + 5);                 // Wout's group 2
+    } else {
+      // the head after the next (head 4: Wout's first half), unless it rides in the next head's projections;
+      // after head 5 Wout's second half, with nothing to ride in
+      if (h + 1 == FR_H || !SPREAD) dma_img(3 * h + 6);
+    }
   }
-  // second half of the out-projection image (buffer 1, read by head 5 until the barrier above)
-  dma(pack + FR_H * FR_QKV_IMG + FR_QKV_IMG, wbuf + FR_QKV_IMG, FR_PIECES);
-  // (running token tile 0's output features 0 .. 95, buffer 0's rows, before this barrier measured neutral:
-  // 101.9 / 102.4 vs 101.3 / 101.9 µs, profiles/r04/ab_feat_rows_dma_spread.txt)
-  dma_wait();
-  __syncthreads();
+  if constexpr (NSLOT == 6) sync_all();  // the image's second half landed
 
-  // ---- per token tile: Y^T = Wout . O^T over K = 192 (K-step h = head h), image [192][FR_ST],
-  //      then residual + LayerNorm per token (lane = token n, 48 of its 192 features)
+  // ---- Y^T = Wout . O^T over K = 192 (K-step h = head h), then residual + LayerNorm per token (lane = token n,
+  //      48 of its 192 features).  Two token tiles per pass share every Wout fragment read from LDS (one
+  //      ds_read_b128 per two MFMAs; a tile's own chain runs over h = 0 .. 5 as ever).  The image [192][FR_ST] is
+  //      read in its six 32-row groups (Y^T tiles 2 gr, 2 gr + 1).  Six slots hold all of it.  Through three slots it
+  //      streams once per pass, item 18 + 6 pass + gr: the first three are under way (above); the barrier after an
+  //      item's MFMAs publishes the next item and frees the slot for the item three on, so a group has two steps to
+  //      land.  (A three-tile row so reads the image twice, 156 KB per block instead of 78 KB, out of L2.)
+  //      The four-tile form (one wave per SIMD, accumulators in AGPRs) keeps one tile per pass, as it was.
+  constexpr int TPP = NT == 4 ? 1 : 2;  // token tiles per pass
+  constexpr int NPASS = (NTQ + TPP - 1) / TPP, NITEM = FR_QKV_GRPS + 6 * (NSLOT == 3 ? NPASS : 1);
 #pragma unroll
-  for (int tt = Q0; tt < NT; ++tt) {
-    f32x4 y[FR_E / 16];
-#pragma unroll
-    for (int f = 0; f < FR_E / 16; ++f) {
-      y[f] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int pass = 0; pass < NPASS; ++pass) {
+    const int t0 = Q0 + TPP * pass, nt = NT - t0 < TPP ? NT - t0 : TPP;  // the pass's tiles t0 .. t0 + nt - 1
+    if constexpr (NPARK > 0) {  // the pass's parked fragments back into registers
 #pragma unroll
       for (int h = 0; h < FR_H; ++h)
-        y[f] = mfma16x(*(const X8*)(wbuf + (16 * f + n) * FR_ST + 32 * h + 8 * g), of[h][tt - Q0], y[f]);
+#pragma unroll
+        for (int k = 0; k < nt; ++k) {
+          const int ps = fr_park<NT, LAST>(h, t0 + k);
+          if (ps >= 0) of[h][t0 + k - Q0] = *(const X8*)(park + ps * FR_FRAG);
+        }
     }
-    const int t = 16 * tt + n;
-    const bool pad = tt == NT - 1 && t >= T;
-    const bool valid = rowok && !pad && (!LAST || t == T - 1);
-    // fp32 state: the residual / output pieces are 4 features at 16 f + 4 g (the Y^T rows of the lane)
-    char* const xr = (char*)xrow + xoff[tt] - 16 * g;
-    float sm = 0.f;
-    if constexpr (F16) {  // the residual is the lane's own X fragments (image rows permuted to match)
+    f32x4 y[TPP][FR_E / 16];
+#pragma unroll
+    for (int f = 0; f < FR_E / 16; ++f) {
+      const int item = FR_QKV_GRPS + (NSLOT == 3 ? 6 * pass : 0) + f / 2;  // (image group f / 2, rows 16 (f % 2) ..)
+      const int wrow = 32 * (item % NSLOT) + 16 * (f % 2);  // its first row in the ring (six slots: 16 f)
+#pragma unroll
+      for (int k = 0; k < nt; ++k) y[k][f] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int h = 0; h < FR_H; ++h) {
+        const X8 w = *(const X8*)(wbuf + (wrow + n) * FR_ST + 32 * h + 8 * g);
+#pragma unroll
+        for (int k = 0; k < nt; ++k) y[k][f] = mfma16x(w, of[h][t0 + k - Q0], y[k][f]);
+      }
+      if (NSLOT == 3 && f % 2 == 1 && item + 1 < NITEM) {  // the group is read
+        if (item + 2 < NITEM) sync_but_last();
+        else sync_all();
+        if (item + 3 < NITEM) dma_grp(item + 3);
+      }
+    }
+    // (bf16 form: its residual loads stay behind the out-projection, which bounds the live registers)
+    if constexpr (!F16) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int k = 0; k < nt; ++k) {
+      const int tt = t0 + k;
+      const int t = 16 * tt + n;
+      const bool pad = tt == NT - 1 && t >= T;
+      const bool valid = rowok && !pad && (!LAST || t == T - 1);
+      // fp32 state: the residual / output pieces are 4 features at 16 f + 4 g (the Y^T rows of the lane)
+      char* const xr = (char*)xrow + xoff[tt] - 16 * g;
+      float sm = 0.f;
+      if constexpr (F16) {  // the residual is the lane's own X fragments (image rows permuted to match)
+#pragma unroll
+        for (int f = 0; f < FR_E / 16; ++f)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            y[k][f][i] += (float)xf[tt][f >> 1][4 * (f & 1) + i];
+            sm += y[k][f][i];
+          }
+      } else {
+#pragma unroll
+        for (int f = 0; f < FR_E / 16; ++f) {
+          const f32x4 xv = *(const f32x4*)(xr + 64 * f);
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            y[k][f][i] += xv[i];
+            sm += y[k][f][i];
+          }
+        }
+      }
+      const float mean = sum_rows4(sm) * (1.0f / FR_E);
+      float q = 0.f;
 #pragma unroll
       for (int f = 0; f < FR_E / 16; ++f)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          y[f][i] += (float)xf[tt][f >> 1][4 * (f & 1) + i];
-          sm += y[f][i];
+          const float dl = y[k][f][i] - mean;
+          q += dl * dl;
         }
-    } else {
+      const float rs = 1.0f / sqrtf(sum_rows4(q) * (1.0f / FR_E) + eps);
+      if (valid) {
+        if constexpr (F16) {  // features 32k + 8g .. +7 from tiles 2k, 2k+1: one 16-B store each
 #pragma unroll
-      for (int f = 0; f < FR_E / 16; ++f) {
-        const f32x4 xv = *(const f32x4*)(xr + 64 * f);
+          for (int c = 0; c < FR_E / 32; ++c) {
+            f16x8 ov;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          y[f][i] += xv[i];
-          sm += y[f][i];
-        }
-      }
-    }
-    const float mean = sum_rows4(sm) * (1.0f / FR_E);
-    float q = 0.f;
+            for (int i = 0; i < 4; ++i)
+              ov[i] = (f16)((y[k][2 * c][i] - mean) * rs), ov[4 + i] = (f16)((y[k][2 * c + 1][i] - mean) * rs);
+            *(f16x8*)(xrow + xoff[tt] + 64 * c) = ov;
+          }
+        } else {
 #pragma unroll
-    for (int f = 0; f < FR_E / 16; ++f)
+          for (int f = 0; f < FR_E / 16; ++f) {
+            f32x4 ov;
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const float dl = y[f][i] - mean;
-        q += dl * dl;
-      }
-    const float rs = 1.0f / sqrtf(sum_rows4(q) * (1.0f / FR_E) + eps);
-    if (valid) {
-      if constexpr (F16) {  // features 32k + 8g .. +7 from tiles 2k, 2k+1: one 16-B store each
-#pragma unroll
-        for (int k = 0; k < FR_E / 32; ++k) {
-          f16x8 ov;
-#pragma unroll
-          for (int i = 0; i < 4; ++i)
-            ov[i] = (f16)((y[2 * k][i] - mean) * rs), ov[4 + i] = (f16)((y[2 * k + 1][i] - mean) * rs);
-          *(f16x8*)(xrow + xoff[tt] + 64 * k) = ov;
-        }
-      } else {
-#pragma unroll
-        for (int f = 0; f < FR_E / 16; ++f) {
-          f32x4 ov;
-#pragma unroll
-          for (int i = 0; i < 4; ++i) ov[i] = (y[f][i] - mean) * rs;
-          *(f32x4*)(xr + 64 * f) = ov;
+            for (int i = 0; i < 4; ++i) ov[i] = (y[k][f][i] - mean) * rs;
+            *(f32x4*)(xr + 64 * f) = ov;
+          }
         }
       }
     }
