@@ -288,6 +288,28 @@ int mmpfn_set_parity_attention_min_keys(int n, int form);
  * out-projection runs inside the MLP kernel there -- mmpfn_outproj_mlp_ln below is the tap on that).  X: device [T][S][E] fp32, the engine's
  * token-major state of ONE member (reference order [S][T][E] transposed).  `rows` = S * T. */
 int mmpfn_feature_attention(mmpfn_ctx* ctx, int layer, float* X, int S, int T, int precision);
+/* The same sublayer, X <- LN(X + FeatAttn_layer(X)), in every form the forwards run it: X is device [M][T][S][E] fp32,
+ * the states of M members one behind the other (a batched forward's state), through the host function the forwards'
+ * layers call.  mmpfn_feature_attention is the M = 1, last = 0 call of this one.
+ * Which kernel runs, by (precision, T):
+ *   MMPFN_PREC_BF16*, T <= 64   feat_rows_kernel on the fp32 state: one wave per table row, all M * S rows in one
+ *                               launch (a 4-row block may hold rows of two members); 1 .. 4 token tiles of 16 by T
+ *                               (T <= 16, 32, 48, 64), the three-tile full form with its last tile's attention output
+ *                               parked in LDS.
+ *   MMPFN_PREC_F16*,  T <= 64   the same kernel's fp16 form on an fp16 copy of the state (out-projection rows
+ *                               permuted, the residual taken from the row's own fragments).
+ *   MMPFN_PREC_F16*,  T > 64    run as MMPFN_PREC_BF16: bit for bit that mode's result.
+ *   MMPFN_PREC_BF16*, T > 64,   the general path, member by member: the q|k|v projection GEMM, the key-tiled attention
+ *   MMPFN_PREC_F32_MFMA         kernel (64-key tiles, fixed-reference softmax), the out-projection + LayerNorm GEMM.
+ *   MMPFN_PREC_F32              the general path on split-bf16 products; T <= 64 on the one-wave-per-(row, head)
+ *                               parity attention kernel, T > 64 on the key-tiled one.
+ * last != 0: the form of a forward's pruned last layer, which reads this sublayer's output at the target token T - 1
+ * only.  feat_rows_kernel then computes and stores token T - 1 of every row alone -- bit for bit what last = 0 stores
+ * there -- and leaves every other token of X as it was (MMPFN_PREC_F16*: as the fp16 copy holds it).  The general path
+ * ignores `last` and runs in full.
+ * MMPFN_ERR_INVALID (mmpfn_last_error says which) for S <= 0, T <= 0, M <= 0, a layer outside [0, nlayers) or an
+ * unknown precision; a null ctx or X returns it without a message; nothing is launched then. */
+int mmpfn_feature_attention_ex(mmpfn_ctx* ctx, int layer, float* X, int S, int T, int M, int last, int precision);
 /* train rows [0, N) attend their own heads, rows [N, S) head 0's K/V (MQA) */
 int mmpfn_item_attention_block(mmpfn_ctx* ctx, int layer, float* X, int S, int T, int N, int precision);
 int mmpfn_mlp_ln(mmpfn_ctx* ctx, int layer, float* X, int64_t rows, int precision);

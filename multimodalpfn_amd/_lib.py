@@ -122,6 +122,7 @@ SIGNATURES = [
     ("mmpfn_cache_free", None, [_vp, _vp]),
     ("mmpfn_kernel_timing", _i, [_vp, _i]),
     ("mmpfn_feature_attention", _i, [_vp, _i, _vp, _i, _i, _i]),
+    ("mmpfn_feature_attention_ex", _i, [_vp, _i, _vp, _i, _i, _i, _i, _i]),
     ("mmpfn_item_attention_block", _i, [_vp, _i, _vp, _i, _i, _i, _i]),
     ("mmpfn_mlp_ln", _i, [_vp, _i, _vp, _i64, _i]),
     ("mmpfn_outproj_mlp_ln", _i, [_vp, _i, _vp, _vp, _i64, _i]),

@@ -1296,14 +1296,19 @@ static int tap_check(mmpfn_ctx* ctx, int layer, const void* X, int precision) {
   return MMPFN_OK;
 }
 
-int mmpfn_feature_attention(mmpfn_ctx* ctx, int layer, float* X, int S, int T, int precision) {
+int mmpfn_feature_attention_ex(mmpfn_ctx* ctx, int layer, float* X, int S, int T, int M, int last, int precision) {
   RC(tap_check(ctx, layer, X, precision));
   if (S <= 0 || T <= 0) return fail(ctx, MMPFN_ERR_INVALID, "bad state geometry");
-  RC(lane_workspace(ctx, S, T, 64, 1, false));  // (a tap runs on the caller's state)
+  if (M <= 0) return fail(ctx, MMPFN_ERR_INVALID, "bad member count");
+  RC(lane_workspace(ctx, S, T, 64, M, false));  // (a tap runs on the caller's state)
   const PrecMode pm = decode_prec(precision, T);
-  return state_tap(ctx, X, (int64_t)S * T * ctx->d.emsize, pm, [&](void* Xs) {
-    return feat_sublayer(ctx, ctx->w.layers[layer], Xs, S, T, 1, pm);
+  return state_tap(ctx, X, (int64_t)M * S * T * ctx->d.emsize, pm, [&](void* Xs) {
+    return feat_sublayer(ctx, ctx->w.layers[layer], Xs, S, T, M, pm, last != 0);
   });
+}
+
+int mmpfn_feature_attention(mmpfn_ctx* ctx, int layer, float* X, int S, int T, int precision) {
+  return mmpfn_feature_attention_ex(ctx, layer, X, S, T, 1, 0, precision);
 }
 
 int mmpfn_item_attention_block(mmpfn_ctx* ctx, int layer, float* X, int S, int T, int N, int precision) {

@@ -590,6 +590,21 @@ class HipEngine:
         return self._state_tap(X, self.lib.mmpfn_feature_attention,
                                lambda Xt, S, T: (layer, _ptr(Xt), S, T, precision))
 
+    def feature_attention_ex(self, layer: int, X: torch.Tensor, precision: int, last: bool = False) -> torch.Tensor:
+        """The same sublayer on the states of M members in one call, ``X`` ``[M, S, T, E]`` (each in reference
+        order), through ``mmpfn_feature_attention_ex``: every form the forwards run it in.  ``last``: the pruned
+        last layer's form, which on the row-resident kernel updates token T - 1 of every row alone."""
+        Xd = self._dev(X)
+        if Xd.dim() != 4:
+            raise ValueError(f"X must be [M, S, T, E], got {tuple(Xd.shape)}")
+        Xt = torch.empty((Xd.shape[0], Xd.shape[2], Xd.shape[1], Xd.shape[3]), dtype=Xd.dtype, device=Xd.device)
+        Xt.copy_(Xd.transpose(1, 2))  # a new tensor always (see _state_tap)
+        M, T, S, _ = Xt.shape
+        self._bind_stream()
+        self._check(self.lib.mmpfn_feature_attention_ex(self.ctx, layer, _ptr(Xt), S, T, M, int(last), precision),
+                    "mmpfn_feature_attention_ex")
+        return Xt.transpose(1, 2).contiguous()
+
     def item_attention_block(self, layer: int, X: torch.Tensor, n_train: int, precision: int) -> torch.Tensor:
         """``LN(X + ItemAttn_layer(X))`` (layer.py:341-379) through ``mmpfn_item_attention_block``."""
         return self._state_tap(X, self.lib.mmpfn_item_attention_block,
