@@ -1,13 +1,20 @@
 // Attention kernels of the PerFeatureEncoderLayer (layer.py:332-395,
 // multi_head_attention.py:547-736) for gfx950.
 //
-// One MFMA flash-attention kernel serves both axes:
-//  * sample axis (attn_between_items): batch = token column t, queries = rows s,
-//    4 waves x 32 queries per block -- the dominant cost of the forward;
-//  * feature axis (attn_between_features): batch = row s, queries = keys = the T
-//    tokens of that row, one wave per block.
+// This file holds the attention of the fp32 modes, the generic batched kernel, and the one entry to the
+// sample-axis (item) attention of every mode:
+//  * attn_item_kernel<MODE, NW>: MFMA flash attention over a batch of independent sequences (launch_attn), lazily
+//    rescaled running max.  Four waves x 32 queries per block: PREC_F32_MFMA's item attention (batch = token
+//    column t, queries = rows s); one wave per block: the feature attention (batch = row s, queries = keys = the
+//    row's T tokens) of PREC_F32_MFMA, of PREC_F32 past 64 tokens (split-bf16 products), and a bf16 form;
+//  * attn_feat3_kernel: PREC_F32's feature attention for T <= 64, one wave per (row, head), no LDS;
+//  * attn_item3_kernel<CHEAP>: PREC_F32's item attention on split-bf16 operands, on the task map of attn_item.h;
+//  * launch_attn_layer: a layer's item attention in any mode.  It builds the task map (Attn2Args, attn_item.h)
+//    and launches attn_item3_kernel, or hands it to attention_pipe.hip (launch_attn_pipe: the 16-bit modes'
+//    software-pipelined kernel), or launches attn_item_kernel<0, 4> twice for PREC_F32_MFMA.
+// The 16-bit modes' feature attention is the row-resident sublayer of featrow.hip.
 //
-// Sample-axis details:
+// attn_item_kernel on the sample axis:
 //    For token column t and head h, query rows s in [s0, s0+nq) attend to keys
 //    [0, nk) (the train rows).  Train queries use their own head's K/V; test queries
 //    use head 0's K/V for every head (reuse_first_head_kv, layer.py:344-358) via
@@ -22,6 +29,7 @@
 //      f32  : v_mfma_f32_32x32x2_f32 (parity mode; exact fp32 fma chains)
 #include <atomic>
 
+#include "attn_item.h"
 #include "common.h"
 #include "kernels.h"
 
@@ -52,15 +60,6 @@ struct IaLds {
 //           sum_k p into every register of lacc, moving the adds off the VALU.
 constexpr float IA_TAU = 8.0f;
 
-// hi = bf16(x), lo = bf16(x - hi) of 8 fp32 values (the parity mode's split operands)
-__device__ __forceinline__ void split8v(f32x4 a, f32x4 b, bf16x8& hi, bf16x8& lo) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    hi[i] = (bf16)a[i], hi[4 + i] = (bf16)b[i];
-    lo[i] = (bf16)(a[i] - (float)hi[i]), lo[4 + i] = (bf16)(b[i] - (float)hi[4 + i]);
-  }
-}
-
 // MODE 0: fp32-input MFMA (PREC_F32_MFMA), 1: bf16, 2: parity mode on fp32 data with split-bf16 operands
 // (three products per contraction, like attn_item3); modes 0 and 2 share the fp32 LDS images
 template <int MODE, int NW>
@@ -82,8 +81,7 @@ __global__ __launch_bounds__(64 * NW) void attn_item_kernel(const AttnArgs p) {
     const int gx = gridDim.x, gy = gridDim.y;
     const int nb = gx * gy * gridDim.z;
     const int pid = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
-    const int xcd = pid & 7, slot = pid >> 3;
-    const int lid = xcd * (nb >> 3) + min(xcd, nb & 7) + slot;
+    const int lid = xcd_task(pid, nb);
     qblk = lid % gx;
     const int rest = lid / gx;
     h = rest % gy;
@@ -106,10 +104,7 @@ __global__ __launch_bounds__(64 * NW) void attn_item_kernel(const AttnArgs p) {
     const float* qrow = (const float*)Q + qs * 32;
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-      f32x4 a = *(const f32x4*)(qrow + 16 * ks + 8 * hh), b = *(const f32x4*)(qrow + 16 * ks + 8 * hh + 4);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) a[i] *= c, b[i] *= c;
-      split8v(a, b, qb[ks], ql[ks]);
+      split_bf16(*(const f32x4*)(qrow + 16 * ks + 8 * hh), *(const f32x4*)(qrow + 16 * ks + 8 * hh + 4), c, qb[ks], ql[ks]);
     }
   } else if constexpr (BF16) {
     const bf16* qrow = (const bf16*)Q + qs * 32;
@@ -218,7 +213,7 @@ __global__ __launch_bounds__(64 * NW) void attn_item_kernel(const AttnArgs p) {
         bf16x8 kh[2], kl[2];
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks)
-          split8v(*(const f32x4*)(krow + (16 * ks + 8 * hh) * 4), *(const f32x4*)(krow + (16 * ks + 8 * hh + 4) * 4),
+          split_bf16(*(const f32x4*)(krow + (16 * ks + 8 * hh) * 4), *(const f32x4*)(krow + (16 * ks + 8 * hh + 4) * 4),
                   kh[ks], kl[ks]);
         sacc[u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kl[0], qb[0], negm, 0, 0, 0);
         sacc[u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kl[1], qb[1], sacc[u], 0, 0, 0);
@@ -311,9 +306,9 @@ __global__ __launch_bounds__(64 * NW) void attn_item_kernel(const AttnArgs p) {
             lsum += pa[j] + pc[j];
           }
           bf16x8 ph, pl, vh, vl;
-          split8v(pa, pc, ph, pl);
+          split_bf16(pa, pc, ph, pl);
           const int kb = 32 * u + 16 * sp + 4 * hh;
-          split8v(*(const f32x4*)(vrow + kb * 4), *(const f32x4*)(vrow + (kb + 8) * 4), vh, vl);
+          split_bf16(*(const f32x4*)(vrow + kb * 4), *(const f32x4*)(vrow + (kb + 8) * 4), vh, vl);
           o = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vl, ph, o, 0, 0, 0);
           o = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vh, pl, o, 0, 0, 0);
           o = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vh, ph, o, 0, 0, 0);
@@ -422,7 +417,7 @@ __global__ __launch_bounds__(256, 2) void attn_feat3_kernel(const AttnArgs p, in
     const float* kr = Kg + (int64_t)min(key, T - 1) * 32;
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks)
-      split8v(*(const f32x4*)(kr + 16 * ks + 8 * hh), *(const f32x4*)(kr + 16 * ks + 8 * hh + 4), kh[u][ks], kl[u][ks]);
+      split_bf16(*(const f32x4*)(kr + 16 * ks + 8 * hh), *(const f32x4*)(kr + 16 * ks + 8 * hh + 4), kh[u][ks], kl[u][ks]);
 #pragma unroll
     for (int sp = 0; sp < 2; ++sp) {
       const int kb = 32 * u + 16 * sp + 4 * hh;
@@ -434,7 +429,7 @@ __global__ __launch_bounds__(256, 2) void attn_feat3_kernel(const AttnArgs p, in
         if (kb + j >= T) a[j] = 0.f;
         if (kb + 8 + j >= T) e[j] = 0.f;
       }
-      split8v(a, e, vh[u][sp], vl[u][sp]);
+      split_bf16(a, e, vh[u][sp], vl[u][sp]);
     }
   }
 #pragma unroll
@@ -445,10 +440,7 @@ __global__ __launch_bounds__(256, 2) void attn_feat3_kernel(const AttnArgs p, in
     const float* qr = Q + (int64_t)min(t, T - 1) * 32;
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-      f32x4 a = *(const f32x4*)(qr + 16 * ks + 8 * hh), e = *(const f32x4*)(qr + 16 * ks + 8 * hh + 4);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) a[i] *= c, e[i] *= c;
-      split8v(a, e, qh[ks], ql[ks]);
+      split_bf16(*(const f32x4*)(qr + 16 * ks + 8 * hh), *(const f32x4*)(qr + 16 * ks + 8 * hh + 4), c, qh[ks], ql[ks]);
     }
     f32x16 st[2];
 #pragma unroll
@@ -485,7 +477,7 @@ __global__ __launch_bounds__(256, 2) void attn_feat3_kernel(const AttnArgs p, in
           l += pa[j] + pc[j];
         }
         bf16x8 ph, pl;
-        split8v(pa, pc, ph, pl);
+        split_bf16(pa, pc, ph, pl);
         o = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vl[u][sp], ph, o, 0, 0, 0);
         o = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vh[u][sp], pl, o, 0, 0, 0);
         o = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vh[u][sp], ph, o, 0, 0, 0);
@@ -529,45 +521,6 @@ constexpr int A3_QPB = 4 * A3_QPW;
 static_assert(A3_QPB == ATTN_ITEM_QPB, "one task size for both kernels (capi.cpp item_sublayer aligns the pruned launch to it)");
 constexpr int A3_STAGE = 4 * 4096;  // K hi | K lo | V^T hi | V^T lo
 
-__device__ __forceinline__ void a3_split8(f32x4 a, f32x4 b, float sc, bf16x8& hi, bf16x8& lo) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float x = a[i] * sc, y = b[i] * sc;
-    hi[i] = (bf16)x, hi[4 + i] = (bf16)y;
-    lo[i] = (bf16)(x - (float)hi[i]), lo[4 + i] = (bf16)(y - (float)hi[4 + i]);
-  }
-}
-
-// exact two-pass softmax for one query per lane, fp32 K / V^T straight from global memory
-__device__ __attribute__((noinline)) void a3_exact_rows(const Attn2Args& p, const float* Kg, const float* Vg,
-                                                         const float* qrow, float* orow, bool valid, float c) {
-  float q[32], o[32];
-#pragma unroll
-  for (int d = 0; d < 32; ++d) q[d] = qrow[d] * c, o[d] = 0.f;
-  float m = -INFINITY;
-  for (int k = 0; k < p.nk; ++k) {
-    float s = 0.f;
-#pragma unroll
-    for (int d = 0; d < 32; ++d) s = fmaf(q[d], Kg[(int64_t)k * 32 + d], s);
-    m = fmaxf(m, s);
-  }
-  float l = 0.f;
-  for (int k = 0; k < p.nk; ++k) {
-    float s = 0.f;
-#pragma unroll
-    for (int d = 0; d < 32; ++d) s = fmaf(q[d], Kg[(int64_t)k * 32 + d], s);
-    const float e = exp2f(s - m);
-    l += e;
-#pragma unroll
-    for (int d = 0; d < 32; ++d) o[d] = fmaf(e, Vg[(int64_t)d * p.Npad + k], o[d]);
-  }
-  if (valid) {
-    const float inv = 1.0f / l;
-#pragma unroll
-    for (int d = 0; d < 32; d += 4) *(f32x4*)(orow + d) = f32x4{o[d] * inv, o[d + 1] * inv, o[d + 2] * inv, o[d + 3] * inv};
-  }
-}
-
 // CHEAP: the measured precision budget of DESIGN 5.7 as an opt-in (the launcher picks it when the sequence has
 // >= x3_cheap_min_keys keys, default never; profiles/r06/parity_n0_sweep_form*.txt): bit 0, S = K Q^T on ONE fp16 product (Q, K
 // rounded to fp16); bit 1, P.V on two products (P rounded to bf16 once, V split: Vl Ph + Vh Ph) and the row sums over
@@ -580,11 +533,14 @@ __global__ __launch_bounds__(256, 2) void attn_item3_kernel(const Attn2Args p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, hh = lane >> 5;
 
-  int b, g, chunk;  // task map of attn_pipe_kernel (contiguous task ranges per XCD)
+  // task: block -> column b, kv head g and a chunk of the queries that read that KV sequence; contiguous task ranges
+  // per XCD, so one KV sequence stays in one L2.  This scan of tstart is deliberately written out here and,
+  // identically, in attn_pipe_kernel (attention_pipe.hip): as a shared helper taking Attn2Args by reference it made
+  // the compiler load the whole struct in the prologue (more SGPRs in both kernels, profiles/r09).  Change both
+  // copies together.
+  int b, g, chunk;
   {
-    const int nbk = p.nblocks, pid = blockIdx.x;
-    const int xcd = pid & 7, slot = pid >> 3;
-    const int task = xcd * (nbk >> 3) + min(xcd, nbk & 7) + slot;
+    const int task = xcd_task(blockIdx.x, p.nblocks);
     b = task / p.tasks_per_b;
     const int rem = task - b * p.tasks_per_b;
     g = 0;
@@ -594,7 +550,7 @@ __global__ __launch_bounds__(256, 2) void attn_item3_kernel(const Attn2Args p) {
       if (h < p.H && p.tstart[h] <= rem) g = h, base = p.tstart[h];
     chunk = rem - base;
   }
-  const int cnt = p.na + (g == p.kvb ? p.H * p.nb : 0);
+  const int cnt = item_count(p, g);
   const int jw = chunk * A3_QPB + wave * A3_QPW;
   const bool active = jw < cnt;
 
@@ -609,6 +565,7 @@ __global__ __launch_bounds__(256, 2) void attn_item3_kernel(const Attn2Args p) {
   f16x8 qf16[A3_NCH][2];
 #pragma unroll
   for (int qb = 0; qb < A3_NCH; ++qb) {
+    // item_query (attn_item.h) written out: through the helper this kernel's register allocation changes (+4 VGPRs)
     const int j = jw + 32 * qb + r;
     qok[qb] = j < cnt;
     const int jc = min(j, cnt - 1);
@@ -626,7 +583,7 @@ __global__ __launch_bounds__(256, 2) void attn_item3_kernel(const Attn2Args p) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) qf16[qb][ks][i] = (_Float16)(a[i] * c), qf16[qb][ks][4 + i] = (_Float16)(e[i] * c);
       } else {
-        a3_split8(a, e, c, qfh[qb][ks], qfl[qb][ks]);
+        split_bf16(a, e, c, qfh[qb][ks], qfl[qb][ks]);
       }
     }
   }
@@ -661,11 +618,11 @@ __global__ __launch_bounds__(256, 2) void attn_item3_kernel(const Attn2Args p) {
       for (int i = 0; i < 4; ++i) kk[i] = (_Float16)rk[0][i], kk[4 + i] = (_Float16)rk[1][i];
       *(f16x8*)(Ks + koff_w) = kk;
     } else {
-      a3_split8(rk[0], rk[1], 1.0f, hi, lo);
+      split_bf16(rk[0], rk[1], hi, lo);
       *(bf16x8*)(Ks + koff_w) = hi;
       *(bf16x8*)(Ks + 4096 + koff_w) = lo;
     }
-    a3_split8(rv[0], rv[1], 1.0f, hi, lo);
+    split_bf16(rv[0], rv[1], hi, lo);
     const u32x4 vh = __builtin_bit_cast(u32x4, hi), vl = __builtin_bit_cast(u32x4, lo);
     *(u32x2*)(Ks + 8192 + voff_w0) = u32x2{vh.x, vh.y};
     *(u32x2*)(Ks + 8192 + voff_w1) = u32x2{vh.z, vh.w};
@@ -850,7 +807,7 @@ __global__ __launch_bounds__(256, 2) void attn_item3_kernel(const Attn2Args p) {
     float* orow = (float*)p.o + ((int64_t)b * p.S + qsrow[qb]) * (p.H * 32) + qh[qb] * 32;
     if (__any((__float_as_uint(ls) & 0x7fffffffu) >= 0x71800000u)) {
       const float* qrow = (const float*)p.q + (((int64_t)b * p.H + qh[qb]) * p.S + qsrow[qb]) * 32;
-      a3_exact_rows(p, Kg, Vg, qrow, orow, qok[qb] && hh == 0, c);
+      exact_rows(p, Kg, Vg, qrow, orow, qok[qb] && hh == 0, c);
       continue;
     }
     const float inv = 1.0f / ls;

@@ -40,8 +40,10 @@
 // (DESIGN 5.7); the kernel-level tap with fp16 Q / K (mmpfn_item_attention_layer_ex codes 5-7) runs <F8, true, true>.
 #include <type_traits>
 
+#include "attn_item.h"
 #include "common.h"
 #include "kernels.h"
+#include "lds_dma.h"
 
 namespace mmpfn {
 
@@ -122,60 +124,6 @@ constexpr int SG_VALU = 0x2, SG_MFMA = 0x8, SG_VMEM_READ = 0x20, SG_DS_READ = 0x
 #ifndef P4_DMA
 #define P4_DMA 1
 #endif
-// "m0" in the clobber list: clang keeps m0 reserved and ignores the entry (-Winline-asm; the ISA is identical with
-// and without it), and every m0 use the compiler emits itself is preceded by its own write -- test_codegen checks
-// that no m0 read other than these DMA issues exists in the kernels
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-__device__ __forceinline__ void p4_dma16(uint32_t voff, const void* sbase, unsigned lds_dst) {
-  // m0 = the wave's LDS destination; lane i's 16 B (sbase + voff) land at m0 + 16 i.  In inline asm so the
-  // compiler's waitcnt pass adds no vmcnt(0) for it; the loop waits for its own pieces at the tile barrier
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(lds_dst)
-               : "memory", "m0");
-}
-#pragma clang diagnostic pop
-
-__device__ __forceinline__ f32x16 mfma32(bf16x8 a, bf16x8 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x16 mfma32(f16x8 a, f16x8 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-
-// exact two-pass softmax for one query per lane, K / V^T straight from global memory (backstop)
-template <typename QT, typename OT>
-__device__ __attribute__((noinline)) void p4_exact_rows(const Attn2Args& p, const QT* Kg, const bf16* Vg,
-                                                        const QT* qrow, OT* orow, bool valid, float c) {
-  float q[32], o[32];
-#pragma unroll
-  for (int d = 0; d < 32; ++d) q[d] = (float)qrow[d] * c, o[d] = 0.f;
-  float m = -INFINITY;
-  for (int k = 0; k < p.nk; ++k) {
-    float s = 0.f;
-#pragma unroll
-    for (int d = 0; d < 32; ++d) s = fmaf(q[d], (float)Kg[(int64_t)k * 32 + d], s);
-    m = fmaxf(m, s);
-  }
-  float l = 0.f;
-  for (int k = 0; k < p.nk; ++k) {
-    float s = 0.f;
-#pragma unroll
-    for (int d = 0; d < 32; ++d) s = fmaf(q[d], (float)Kg[(int64_t)k * 32 + d], s);
-    const float e = exp2f(s - m);
-    l += e;
-#pragma unroll
-    for (int d = 0; d < 32; ++d) o[d] = fmaf(e, (float)Vg[(int64_t)d * p.Npad + k], o[d]);
-  }
-  if (valid) {
-    const float inv = 1.0f / l;
-#pragma unroll
-    for (int d = 0; d < 32; ++d) orow[d] = (OT)(o[d] * inv);
-  }
-}
-
 template <int F8, bool QF16, bool OF16>
 __global__ __launch_bounds__(256, 2) void attn_pipe_kernel(const Attn2Args p) {
   typedef typename Op16<QF16>::t QT;    // Q and K elements
@@ -201,14 +149,14 @@ __global__ __launch_bounds__(256, 2) void attn_pipe_kernel(const Attn2Args p) {
   }
 #endif
 
-  // ---- task: the queries that read KV sequence (column b, kv head g) are the own-head rows [a0, a0+na)
-  //      of head g, then, for g == kvb, rows [b0, b0+nb) of all H heads, cut into tasks of 256 (4 waves
-  //      x 64); contiguous task ranges per XCD, so one KV sequence stays in one L2
+  // ---- task: block -> column b, kv head g and a chunk of 256 (4 waves x 64) of the queries that read that KV
+  //      sequence; contiguous task ranges per XCD, so one KV sequence stays in one L2.
+  //      This scan of tstart is deliberately written out here and, identically, in attn_item3_kernel
+  //      (attention.hip): as a shared helper taking Attn2Args by reference it made the compiler load the whole
+  //      struct in the prologue (61 -> 86 SGPRs in this kernel, profiles/r09).  Change both copies together.
   int b, g, chunk;
   {
-    const int nbk = p.nblocks, pid = blockIdx.x;
-    const int xcd = pid & 7, slot = pid >> 3;
-    const int task = xcd * (nbk >> 3) + min(xcd, nbk & 7) + slot;
+    const int task = xcd_task(blockIdx.x, p.nblocks);
     b = task / p.tasks_per_b;
     const int rem = task - b * p.tasks_per_b;
     g = 0;
@@ -218,7 +166,7 @@ __global__ __launch_bounds__(256, 2) void attn_pipe_kernel(const Attn2Args p) {
       if (h < p.H && p.tstart[h] <= rem) g = h, base = p.tstart[h];
     chunk = rem - base;
   }
-  const int cnt = p.na + (g == p.kvb ? p.H * p.nb : 0);
+  const int cnt = item_count(p, g);
   const int jw = chunk * P4_QPB + wave * P4_QPW;
   const bool active = jw < cnt;  // wave-uniform; an idle wave only stages its share of every tile
 
@@ -229,27 +177,11 @@ __global__ __launch_bounds__(256, 2) void attn_pipe_kernel(const Attn2Args p) {
   const float c = kLog2e * 0.17677669529663687f;  // log2(e)/sqrt(32)
 
   // the lane's query of chain qb: head and table row (recomputed after the tile loop rather than kept live)
-  struct QRow {
-    int h, s;
-    bool ok;
-  };
-  auto qrow_of = [&](int qb) __attribute__((always_inline)) {
-    const int j = jw + 32 * qb + r;
-    const int jc = min(j, cnt - 1);
-    QRow q;
-    q.ok = j < cnt;
-    if (jc < p.na) {
-      q.h = g, q.s = p.a0 + jc;
-    } else {
-      const int jj = jc - p.na;
-      q.h = jj / p.nb, q.s = p.b0 + jj % p.nb;
-    }
-    return q;
-  };
+  auto qrow_of = [&](int qb) __attribute__((always_inline)) { return item_query(p, g, cnt, jw + 32 * qb + r); };
   Q8 qf[P4_NCH][2];
 #pragma unroll
   for (int qb = 0; qb < P4_NCH; ++qb) {
-    const QRow q = qrow_of(qb);
+    const ItemQuery q = qrow_of(qb);
     const QT* qrow = (const QT*)p.q + (((int64_t)b * p.H + q.h) * p.S + q.s) * 32;
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
@@ -343,8 +275,8 @@ __global__ __launch_bounds__(256, 2) void attn_pipe_kernel(const Attn2Args p) {
   }
   const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)ring;
   auto dma = [&](int t, int slot) __attribute__((always_inline)) {  // tile t -> ring slot (wave-uniform)
-    p4_dma16(kdo, Kg + (int64_t)t * (P4_KT * 32), __builtin_amdgcn_readfirstlane(lds0 + slot * P4_SLOT_BYTES + wave * 1024));
-    p4_dma16(vdo, Vg + t * P4_KT,
+    lds_dma16(kdo, Kg + (int64_t)t * (P4_KT * 32), __builtin_amdgcn_readfirstlane(lds0 + slot * P4_SLOT_BYTES + wave * 1024));
+    lds_dma16(vdo, Vg + t * P4_KT,
              __builtin_amdgcn_readfirstlane(lds0 + slot * P4_SLOT_BYTES + VBASE + wave * 1024));
   };
   // staging registers: P4_LEAD = 1: one set, tile t+3 loaded in step t and written to LDS in step t+1;
@@ -439,8 +371,8 @@ __global__ __launch_bounds__(256, 2) void attn_pipe_kernel(const Attn2Args p) {
   auto smm = [&](f32x16(&s)[2], const Q8(&kf)[2][2], int qb) __attribute__((always_inline)) {
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
-      s[u] = mfma32(kf[u][0], qf[qb][0], zero16);
-      s[u] = mfma32(kf[u][1], qf[qb][1], s[u]);
+      s[u] = mfma32x(kf[u][0], qf[qb][0], zero16);
+      s[u] = mfma32x(kf[u][1], qf[qb][1], s[u]);
     }
   };
   // bf16 P.V of one (tile, chain): the re-run tile of every variant
@@ -457,8 +389,8 @@ __global__ __launch_bounds__(256, 2) void attn_pipe_kernel(const Attn2Args p) {
     for (int u = 0; u < 2; ++u)
 #pragma unroll
       for (int sp = 0; sp < 2; ++sp) {
-        o[qb] = mfma32(vf[u][sp], pb[u][sp], o[qb]);
-        lacc[qb] = mfma16(sel, pb[u][sp], lacc[qb]);
+        o[qb] = mfma32x(vf[u][sp], pb[u][sp], o[qb]);
+        lacc[qb] = mfma16x(sel, pb[u][sp], lacc[qb]);
       }
   };
   // F8: per-chain conversion scale of the lane's query (P' = exp2(s) / scale), set from the first tile
@@ -499,8 +431,8 @@ __global__ __launch_bounds__(256, 2) void attn_pipe_kernel(const Attn2Args p) {
       for (int u = 0; u < 2; ++u)
 #pragma unroll
         for (int sp = 0; sp < 2; ++sp) {
-          o[qb] = mfma32(vf[u][sp], pb[u][sp], o[qb]);
-          lacc[qb] = mfma16(sel, pb[u][sp], lacc[qb]);
+          o[qb] = mfma32x(vf[u][sp], pb[u][sp], o[qb]);
+          lacc[qb] = mfma16x(sel, pb[u][sp], lacc[qb]);
         }
     }
   };
@@ -794,11 +726,11 @@ __global__ __launch_bounds__(256, 2) void attn_pipe_kernel(const Attn2Args p) {
 #pragma unroll
   for (int qb = 0; qb < P4_NCH; ++qb) {
     const float ls = rowsum(qb);
-    const QRow q = qrow_of(qb);
+    const ItemQuery q = qrow_of(qb);
     OT* orow = (OT*)p.o + ((int64_t)b * p.S + q.s) * (p.H * 32) + q.h * 32;
     if (__any((__float_as_uint(ls) & 0x7fffffffu) >= 0x71800000u)) {
       const QT* qrow = (const QT*)p.q + (((int64_t)b * p.H + q.h) * p.S + q.s) * 32;
-      p4_exact_rows(p, Kg, Vg, qrow, orow, q.ok && hh == 0, p.q_prescaled ? 1.0f : c);
+      exact_rows(p, Kg, Vg, qrow, orow, q.ok && hh == 0, p.q_prescaled ? 1.0f : c);
       continue;
     }
     const float inv = 1.0f / ls;

@@ -15,6 +15,8 @@
 #include <stdint.h>
 
 #include <atomic>
+#include <type_traits>
+#include <utility>
 
 namespace mmpfn {
 
@@ -68,6 +70,39 @@ __device__ __forceinline__ f32x16 mfma32x(bf16x8 a, bf16x8 b, f32x16 c) {
 }
 __device__ __forceinline__ f32x16 mfma32x(f16x8 a, f16x8 b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+}
+
+// The parity mode's split operands, 8 fp32 values at a time: hi = bf16(x), lo = bf16(x - hi), x = hi + lo to 2^-17
+// relative -- the rounding rule under the 1e-4 parity contract (weight_pack.h split_bf16 is its host form; mlp.hip
+// x3_hi and rowgemm3.hip split_rows3 are the same rule kept written out for their kernels' register allocation)
+__device__ __forceinline__ void split_bf16(const f32x4& a, const f32x4& b, bf16x8& hi, bf16x8& lo) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    hi[i] = (bf16)a[i], hi[4 + i] = (bf16)b[i];
+    lo[i] = (bf16)(a[i] - (float)hi[i]), lo[4 + i] = (bf16)(b[i] - (float)hi[4 + i]);
+  }
+}
+// ... of x * sc: one fp32 multiply per element, then the split
+__device__ __forceinline__ void split_bf16(f32x4 a, f32x4 b, float sc, bf16x8& hi, bf16x8& lo) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) a[i] *= sc, b[i] *= sc;
+  split_bf16(a, b, hi, lo);
+}
+
+// The hardware deals consecutive workgroups round-robin to the 8 XCDs.  Block pid of n -> task id such that XCD x
+// (= pid % 8) works through one contiguous range of tasks, so the blocks that share operands share that XCD's L2.
+__device__ __forceinline__ int xcd_task(int pid, int n) {
+  const int xcd = pid & 7, slot = pid >> 3;
+  return xcd * (n >> 3) + min(xcd, n & 7) + slot;
+}
+
+template <typename F, int... I>
+__device__ __forceinline__ void static_for_(F&& f, std::integer_sequence<int, I...>) {
+  (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, typename F>
+__device__ __forceinline__ void static_for(F&& f) {  // f(integral_constant<int, 0>) .. f(<N - 1>)
+  static_for_(f, std::make_integer_sequence<int, N>{});
 }
 
 constexpr float kLog2e = 1.4426950408889634f;

@@ -39,6 +39,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "lds_dma.h"
 
 namespace mmpfn {
 
@@ -75,18 +76,6 @@ __device__ __forceinline__ X8 cat8(const f32x4& a, const f32x4& b, float s = 1.0
 }
 
 typedef __attribute__((address_space(3))) void lds_void;
-
-// one 1-KB LDS-DMA piece in the saddr form: lane i's 16 B at sbase + voff land at LDS m0 + 16 i (a scalar base per
-// piece and one offset VGPR for all of them; the builtin's 64-bit VGPR address per piece cost ~19 VGPRs at the
-// kernel's register peak).  m0: clang keeps it reserved and ignores the clobber (-Winline-asm); test_codegen checks
-// that every m0 use in the kernels is one of these issues.
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-__device__ __forceinline__ void fr_dma16(uint32_t voff, const void* sbase, unsigned lds_dst) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(lds_dst)
-               : "memory", "m0");
-}
-#pragma clang diagnostic pop
 
 // LAST: the form of a forward's pruned last layer (capi.cpp last_layer_tail), which reads this sublayer's output at
 // the target token T-1 only: K and V of every token tile as ever, but Q, the softmax, P.V and the out-projection
@@ -128,7 +117,7 @@ __global__ __launch_bounds__(256, NT <= 3 ? 2 : 1) void feat_rows_kernel(void* _
     const int grp = item < FR_QKV_GRPS + 6 ? item : item - 6;  // (the short ring's second pass over Wout)
     const char* src = (const char*)(pack + grp * FR_GRP);
     const unsigned dst = lds_u32(wbuf + (item % NSLOT) * FR_GRP);
-    fr_dma16(dvoff, src + p * 1024, __builtin_amdgcn_readfirstlane(dst + p * 1024));
+    lds_dma16(dvoff, src + p * 1024, __builtin_amdgcn_readfirstlane(dst + p * 1024));
   };
   // three slots: a group's 13 pieces are three per wave (dma_part i = 0 .. 2, branch-free) and the 13th by wave 0
   // (dma_tail)

@@ -18,6 +18,7 @@
 // to LDS, so the fp32 residual stream is never materialised in bf16 in HBM.
 #include "common.h"
 #include "kernels.h"
+#include "tile_ring.h"
 
 namespace mmpfn {
 
@@ -38,15 +39,6 @@ struct Stage {
   // raw staged A data per chunk: f32 source feeding bf16 compute needs 32 bytes
   static constexpr int AWORDS = (BF16 && AF32) ? 2 : 1;
 };
-
-// hi = bf16(x), lo = bf16(x - hi): x = hi + lo to 2^-17 relative (parity mode)
-__device__ __forceinline__ void split8(const f32x4& f0, const f32x4& f1, bf16x8& hi, bf16x8& lo) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    hi[i] = (bf16)f0[i], hi[4 + i] = (bf16)f1[i];
-    lo[i] = (bf16)(f0[i] - (float)hi[i]), lo[4 + i] = (bf16)(f1[i] - (float)hi[4 + i]);
-  }
-}
 
 // MODE 0: fp32-input MFMA, 1: bf16, 2: x3 (split bf16, A fp32)
 template <int MODE, bool AF32, bool OF32, int EPI>
@@ -128,7 +120,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmArgs p) {
       u32x4 v;
       if constexpr (X3) {
         bf16x8 hi, lo;
-        split8(__builtin_bit_cast(f32x4, ra[i][0]), __builtin_bit_cast(f32x4, ra[i][AW - 1]), hi, lo);
+        split_bf16(__builtin_bit_cast(f32x4, ra[i][0]), __builtin_bit_cast(f32x4, ra[i][AW - 1]), hi, lo);
         v = __builtin_bit_cast(u32x4, hi);
         *(u32x4*)(Asl + r * ROWB + ach[i] * 16) = __builtin_bit_cast(u32x4, lo);
       } else if (BF16 && AF32) {
@@ -396,38 +388,19 @@ hipError_t launch_t(const GemmArgs& a, int groups, hipStream_t st) {
 // re-reads W once per 64 rows (2.7 GB of L2 traffic at PAD-UFES size); this tile is 256 rows x
 // 256 W rows per 512-thread block (8 waves as 2 x 4, each 128 x 64 = 8 x 4 MFMA-16 tiles), and
 // blocks that share a W tile are scheduled on one XCD back to back so the tile is fetched from
-// HBM about once.  K moves in 32-wide slices through a 4-stage LDS ring filled by LDS-DMA
-// (global_load_lds_dwordx4: no staging registers, no LDS write pass after the MFMAs): slice
-// kt+1..kt+3 are in flight while slice kt computes; one barrier per slice.  LDS images are unpadded
-// 64-B rows with 16-B chunk c of row r at slot c ^ ((r >> 1) & 3) (conflict-free ds_read_b128 for
-// the 16x16x32 operands); the DMA writes lane-linear, so each lane fetches the chunk that belongs
-// at its slot.  The DMA is inline asm so the compiler adds no vmcnt(0) before the LDS reads of
-// the other stages; the kernel waits for its own slices explicitly.
+// HBM about once.  K moves in 32-wide slices through the 4-stage LDS ring of tile_ring.h (LDS-DMA:
+// no staging registers, no LDS write pass after the MFMAs): slice kt+1..kt+3 are in flight while
+// slice kt computes; one barrier per slice.
 // GLU pairs: W rows interleaved in 16-row blocks [a | b] (capi.cpp), so tiles 2q / 2q+1 of a
 // wave are the a / b halves of the same 16 output columns.
-constexpr int GB_M = 256, GB_N = 256, GB_K = 32;
-constexpr int GB_ROW = GB_K * 2;                    // 64-B LDS rows
-constexpr int GB_STAGE = (GB_M + GB_N) * GB_ROW;    // 32 KB
+constexpr int GB_M = 256, GB_N = 256;
+static_assert(GB_M + GB_N == RING_ROWS, "one ring stage");
 #ifndef GB_STAGES
 #define GB_STAGES 4
 #endif
 constexpr int GB_NST = GB_STAGES;                   // ring stages (128 KB)
 constexpr int GB_OST = GB_N / 2 + 8;                // output staging row stride (bf16)
-constexpr int GB_DMA = (GB_M + GB_N) * (GB_ROW / 16) / 512;  // 16-B DMA pieces per thread and slice (4)
 constexpr int GB_MT = GB_M / 32;                    // 16-row MFMA tiles per wave (8)
-
-__device__ __forceinline__ int gb_slot(int r, int c) { return c ^ ((r >> 1) & 3); }
-
-// "m0" in the clobber list: clang keeps m0 reserved and ignores the entry (-Winline-asm; the ISA is identical with
-// and without it), and every m0 use the compiler emits itself is preceded by its own write -- test_codegen checks
-// that no m0 read other than these DMA issues exists in the kernels
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-__device__ __forceinline__ void gb_dma16(const void* src, unsigned lds_base) {
-  // m0 = the wave's LDS destination; lane i's 16 B land at m0 + 16 i
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(lds_base) : "memory", "m0");
-}
-#pragma clang diagnostic pop
 
 // F16: the same kernel on fp16 operands (the fp16 mode's mixer: the reference's autocast runs these Linears in fp16)
 template <bool F16>
@@ -446,62 +419,39 @@ __global__ __launch_bounds__(512, 1) void gemm_glu_big_kernel(const typename Op1
   // W-tile-major, so the M tiles of one W tile run back to back on one L2
   int mt, nt;
   {
-    const int nb = gridDim.x;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int per = nb >> 3, extra = nb & 7;
-    const int t = xcd * per + min(xcd, extra) + slot;
+    const int t = xcd_task(blockIdx.x, gridDim.x);
     nt = t / mtiles, mt = t - nt * mtiles;
   }
   const int m0 = mt * GB_M, n0 = nt * GB_N;
   const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)smem;
 
-  // DMA piece j of this wave: LDS chunk q = (wave * GB_DMA + j) * 64 + lane of the stage image
-  // (rows 0-255 = A, 256-511 = W); row r = q / 4 holds global chunk c with gb_slot(r, c) = q % 4
-  const T* src[GB_DMA];
+  // DMA piece j of this wave: stage rows 0-255 = A, 256-511 = W
+  const T* src[RING_DMA];
 #pragma unroll
-  for (int j = 0; j < GB_DMA; ++j) {
-    const int q = (wave * GB_DMA + j) * 64 + lane, r = q >> 2, c = gb_slot(r, q & 3);
+  for (int j = 0; j < RING_DMA; ++j) {
+    int r, c;
+    ring_piece(wave, lane, j, r, c);
     src[j] = r < GB_M ? A + (int64_t)min(m0 + r, M - 1) * K + c * 8 : W + (int64_t)(n0 + r - GB_M) * K + c * 8;
   }
-  auto dma = [&](int kt) {
-    const unsigned base = lds0 + (kt % GB_NST) * GB_STAGE + wave * GB_DMA * 1024;
-#pragma unroll
-    for (int j = 0; j < GB_DMA; ++j)
-      gb_dma16(src[j] + kt * GB_K, __builtin_amdgcn_readfirstlane(base + j * 1024));
-  };
+  auto dma = [&](int kt) { ring_issue<GB_NST>(src, kt, lds0, wave); };
   f32x4 acc[GB_MT][4];
 #pragma unroll
   for (int a = 0; a < GB_MT; ++a)
 #pragma unroll
     for (int b = 0; b < 4; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  const int nk = K / GB_K;
+  const int nk = K / RING_K;
 #pragma unroll
   for (int i = 0; i < GB_NST - 1; ++i)
     if (i < nk) dma(i);
   for (int kt = 0; kt < nk; ++kt) {
     // this thread's pieces of slice kt have landed (up to two later slices may still fly)
-    const int ahead = min(nk - 1 - kt, GB_NST - 2);
-    if (ahead >= 3) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * GB_DMA) : "memory");
-    else if (ahead == 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * GB_DMA) : "memory");
-    else if (ahead == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(GB_DMA) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    ring_wait<GB_NST - 2>(min(nk - 1 - kt, GB_NST - 2));
     __syncthreads();
     // stage (kt+3) % 4 was last read in slice kt-1, before the barrier above
     if (kt + GB_NST - 1 < nk) dma(kt + GB_NST - 1);
-    const unsigned char* As = smem + (kt % GB_NST) * GB_STAGE;
-    const unsigned char* Ws = As + GB_M * GB_ROW;
     X8 af[GB_MT], bw[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int rb = wn * 64 + i * 16 + fr;
-      bw[i] = *(const X8*)(Ws + rb * GB_ROW + 16 * gb_slot(rb, fg));
-    }
-#pragma unroll
-    for (int i = 0; i < GB_MT; ++i) {
-      const int ra = wm * (GB_M / 2) + i * 16 + fr;
-      af[i] = *(const X8*)(As + ra * GB_ROW + 16 * gb_slot(ra, fg));
-    }
+    ring_read<GB_M>(smem + (kt % GB_NST) * RING_STAGE, wm, wn, fr, fg, af, bw);
 #pragma unroll
     for (int a = 0; a < GB_MT; ++a)
 #pragma unroll
@@ -537,11 +487,10 @@ __global__ __launch_bounds__(512, 1) void gemm_glu_big_kernel(const typename Op1
 // W2[z][E][k]^T + b2[z], the rows remapped head-major into the [S][mgm n_mod][E] token tensor.  The 64 x 192
 // tile of gemm_kernel re-reads its W (one head's 192 x 384) per 64 rows and runs at the L2 -> LDS fill
 // rate (75 us at PAD-UFES size); here 320 rows x the head's 192 outputs per 512-thread block (8 waves as
-// 2 x 4, each 160 x 48 = 10 x 3 MFMA-16 tiles), the same four-stage LDS-DMA ring and swizzled 64-B rows
-// as the GLU kernel (320 + 192 = 512 rows: four 16-B pieces per thread and slice), the M tiles of one
-// head back to back on one XCD.
+// 2 x 4, each 160 x 48 = 10 x 3 MFMA-16 tiles), the same four-stage ring as the GLU kernel (320 + 192 =
+// 512 rows), the M tiles of one head back to back on one XCD.
 constexpr int GR_M = 320, GR_N = 192;
-static_assert(GR_M + GR_N == GB_M + GB_N, "four DMA pieces per thread and K slice, as the GLU kernel");
+static_assert(GR_M + GR_N == RING_ROWS, "one ring stage");
 constexpr int GR_MT = GR_M / 32;  // 16-row tiles per wave (10)
 constexpr int GR_NT = GR_N / 64;  // 16-column tiles per wave (3)
 
@@ -559,57 +508,35 @@ __global__ __launch_bounds__(512, 1) void gemm_remap_big_kernel(const typename O
   const int fr = lane & 15, fg = lane >> 4;
   int mt, z;
   {
-    const int nb = gridDim.x;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int per = nb >> 3, extra = nb & 7;
-    const int t = xcd * per + min(xcd, extra) + slot;
+    const int t = xcd_task(blockIdx.x, gridDim.x);
     z = t / mtiles, mt = t - z * mtiles;
   }
   const int m0 = mt * GR_M;
   const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)smem;
-  const T* src[GB_DMA];
+  const T* src[RING_DMA];
 #pragma unroll
-  for (int j = 0; j < GB_DMA; ++j) {
-    const int q = (wave * GB_DMA + j) * 64 + lane, r = q >> 2, c = gb_slot(r, q & 3);
+  for (int j = 0; j < RING_DMA; ++j) {
+    int r, c;
+    ring_piece(wave, lane, j, r, c);
     src[j] = r < GR_M ? A + (int64_t)min(m0 + r, M - 1) * lda + (int64_t)z * K + c * 8
                       : W + ((int64_t)z * GR_N + (r - GR_M)) * K + c * 8;
   }
-  auto dma = [&](int kt) {
-    const unsigned base = lds0 + (kt % GB_NST) * GB_STAGE + wave * GB_DMA * 1024;
-#pragma unroll
-    for (int j = 0; j < GB_DMA; ++j)
-      gb_dma16(src[j] + kt * GB_K, __builtin_amdgcn_readfirstlane(base + j * 1024));
-  };
+  auto dma = [&](int kt) { ring_issue<GB_NST>(src, kt, lds0, wave); };
   f32x4 acc[GR_MT][GR_NT];
 #pragma unroll
   for (int a = 0; a < GR_MT; ++a)
 #pragma unroll
     for (int b = 0; b < GR_NT; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const int nk = K / GB_K;
+  const int nk = K / RING_K;
 #pragma unroll
   for (int i = 0; i < GB_NST - 1; ++i)
     if (i < nk) dma(i);
   for (int kt = 0; kt < nk; ++kt) {
-    const int ahead = min(nk - 1 - kt, GB_NST - 2);
-    if (ahead >= 3) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * GB_DMA) : "memory");
-    else if (ahead == 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * GB_DMA) : "memory");
-    else if (ahead == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(GB_DMA) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    ring_wait<GB_NST - 2>(min(nk - 1 - kt, GB_NST - 2));
     __syncthreads();
     if (kt + GB_NST - 1 < nk) dma(kt + GB_NST - 1);
-    const unsigned char* As = smem + (kt % GB_NST) * GB_STAGE;
-    const unsigned char* Ws = As + GR_M * GB_ROW;
     X8 af[GR_MT], bw[GR_NT];
-#pragma unroll
-    for (int i = 0; i < GR_NT; ++i) {
-      const int rb = wn * (GR_N / 4) + i * 16 + fr;
-      bw[i] = *(const X8*)(Ws + rb * GB_ROW + 16 * gb_slot(rb, fg));
-    }
-#pragma unroll
-    for (int i = 0; i < GR_MT; ++i) {
-      const int ra = wm * (GR_M / 2) + i * 16 + fr;
-      af[i] = *(const X8*)(As + ra * GB_ROW + 16 * gb_slot(ra, fg));
-    }
+    ring_read<GR_M>(smem + (kt % GB_NST) * RING_STAGE, wm, wn, fr, fg, af, bw);
 #pragma unroll
     for (int a = 0; a < GR_MT; ++a)
 #pragma unroll
@@ -674,12 +601,12 @@ hipError_t launch_gemm(const GemmArgs& a, int prec, int epi, bool a_f32, bool ou
 hipError_t launch_gemm_remap_big(const void* A, int64_t lda, const void* W, const float* bias, void* C, DType c_t,
                                  int M, int K, int nheads, int n_mod, int E, hipStream_t st, DType t) {
   if (M <= 0) return hipSuccess;
-  if (E != GR_N || K % GB_K != 0 || K <= 0 || nheads <= 0 || n_mod <= 0) return hipErrorInvalidValue;
+  if (E != GR_N || K % RING_K != 0 || K <= 0 || nheads <= 0 || n_mod <= 0) return hipErrorInvalidValue;
   if (t == DType::F32 || (c_t != DType::F32 && c_t != t)) return hipErrorInvalidValue;
   const bool f16 = t == DType::F16, c_bf16 = c_t != DType::F32;  // c_bf16: C in the operands' 16-bit type
   const int mtiles = (M + GR_M - 1) / GR_M;
   const int64_t nb = (int64_t)mtiles * nheads;
-  const int lds = GB_NST * GB_STAGE;
+  const int lds = GB_NST * RING_STAGE;
   if (f16) {  // fp16 operands; a 16-bit token output is fp16 too
     if (c_bf16)
       hipLaunchKernelGGL((gemm_remap_big_kernel<_Float16, true>), dim3((unsigned)nb), dim3(512), lds, st,
@@ -700,12 +627,12 @@ hipError_t launch_gemm_remap_big(const void* A, int64_t lda, const void* W, cons
 hipError_t launch_gemm_glu_big(const void* A, const void* W, const float* bias, void* C, int M, int N, int K,
                                hipStream_t st, DType t) {
   if (M <= 0) return hipSuccess;
-  if (N % GB_N != 0 || K % GB_K != 0 || K <= 0 || t == DType::F32) return hipErrorInvalidValue;
+  if (N % GB_N != 0 || K % RING_K != 0 || K <= 0 || t == DType::F32) return hipErrorInvalidValue;
   const bool f16 = t == DType::F16;
   const int mtiles = (M + GB_M - 1) / GB_M;
   const int64_t nb = (int64_t)mtiles * (N / GB_N);
-  const int lds = GB_NST * GB_STAGE;  // 144 KB
-  static_assert(GB_M * GB_OST * 2 <= GB_NST * GB_STAGE, "output staging fits the ring");
+  const int lds = GB_NST * RING_STAGE;  // 144 KB
+  static_assert(GB_M * GB_OST * 2 <= GB_NST * RING_STAGE, "output staging fits the ring");
   if (f16)
     hipLaunchKernelGGL((gemm_glu_big_kernel<true>), dim3((unsigned)nb), dim3(512), lds, st, (const _Float16*)A,
                        (const _Float16*)W, bias, (_Float16*)C, M, N, K, mtiles);

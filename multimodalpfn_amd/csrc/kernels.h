@@ -212,28 +212,6 @@ hipError_t launch_attn_layer(const AttnLayerArgs& a, int base_prec, hipStream_t 
 hipError_t launch_vt_fp8(const void* vt, void* vt8, int64_t n, hipStream_t st);
 int set_x3_cheap_min_keys(int n, int form);  // previous value; mmpfn_set_parity_attention_min_keys
 
-// The seam between attention.hip (launch_attn_layer: the task map) and attention_pipe.hip (the pipelined kernel), and
-// nothing else's: task map + operands of the sample-axis attention kernels, by value
-struct Attn2Args {
-  const __bf16* q;  // [B][H][S][32]
-  const __bf16* k;  // [B][H][Npad][32]
-  const __bf16* vt; // [B][H][32][Npad]
-  __bf16* o;        // row b*S + s, element row*H*32 + h*32 + d
-  int S, H, Npad, nk;
-  int a0, na;          // own-head query rows
-  int b0, nb, kvb;     // shared-KV query rows (all heads) against kv head kvb
-  int tasks_per_b, nblocks;
-  int tstart[9];       // task prefix per kv head inside one column
-  int64_t kv_bstride;  // elements between the K (V^T) blocks of consecutive columns: H*Npad*32, or
-                       // Npad*32 for a head-0-only train-KV cache
-  int q_prescaled;     // Q already carries log2(e)/sqrt(32) (folded into the engine's bf16 Q weights)
-  const unsigned char* vt8;  // f8 != 0: V^T in e4m3, the layout of vt
-  int f8;              // P.V on fp8 MFMA: 0 off (bf16), 1 P in e4m3, 2 P in e5m2 (attention_pipe.hip)
-  int qk_f16;          // q, k and o hold fp16 (S on f16 MFMA; the fp16 tap); vt stays bf16
-  int o_f16;           // PREC_F16's forward: q, k bf16, o fp16 (every MFMA a bf16 one)
-};
-hipError_t launch_attn_pipe(const Attn2Args& a, hipStream_t st);
-
 // ---- encoders / decoder ------------------------------------------------------------
 struct SlotParams {  // per (group, slot): how to transform raw column -> model input
   int src;           // source column or -1 (zero fill)

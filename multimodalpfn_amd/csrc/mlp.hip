@@ -236,6 +236,8 @@ constexpr int X3_W1P = X3_HC * ME * 2;           // W1 chunk plane: 32 rows x 38
 constexpr int X3_W2P = ME * X3_HC * 2;           // W2 chunk plane: 192 rows x 64 B
 constexpr int X3_LDS = 2 * X3_W1P + 2 * X3_W2P;  // 48 KB
 
+// the same rule as split_bf16 (common.h), kept written out: through split_bf16 mlp_x3_kernel takes 216 VGPRs for 212
+// (profiles/r09)
 __device__ __forceinline__ bf16x8 x3_hi(const f32x4& a, const f32x4& b, bf16x8& lo) {
   bf16x8 hi;
 #pragma unroll

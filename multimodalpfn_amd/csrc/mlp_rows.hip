@@ -28,6 +28,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "lds_dma.h"
 
 namespace mmpfn {
 
@@ -41,34 +42,6 @@ constexpr int W2RING = NSLOT * SLOT_B;     // byte offset of the W2 ring
 constexpr int LDS_B = 2 * NSLOT * SLOT_B;  // 72 KB per block: two blocks per CU
 constexpr int MP = SLOT_B / 1024 / 4;      // 1-KB DMA pieces per wave, matrix and chunk (3)
 typedef __attribute__((ext_vector_type(2))) float float2_t;
-
-// "m0" in the clobber list: clang keeps m0 reserved and ignores the entry (-Winline-asm; the ISA is identical with
-// and without it), and every m0 use the compiler emits itself is preceded by its own write -- test_codegen checks
-// that no m0 read other than these DMA issues exists in the kernels
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-__device__ __forceinline__ void mlp_dma16(uint32_t voff, const void* sbase, unsigned lds_dst) {
-  // m0 = the wave's LDS destination; lane i's 16 B (sbase + voff) land at m0 + 16 i
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(lds_dst)
-               : "memory", "m0");
-}
-#pragma clang diagnostic pop
-
-template <typename F, int... I>
-__device__ __forceinline__ void static_for_(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {  // f(integral_constant<int, 0>) .. f(<N - 1>)
-  static_for_(f, std::make_integer_sequence<int, N>{});
-}
-
-__device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x4 mfma16(f16x8 a, f16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
 
 // TT = 16-row tiles per wave: 2 (32 rows, two waves per SIMD, accumulators in VGPRs) or 4 (64 rows,
 // one wave per SIMD with the 192 x 64 Y^T accumulator in AGPRs -- half the LDS weight reads per row,
@@ -133,8 +106,8 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : (TT == 2 ? 2 : 1)) void mlp_
   const int64_t m0 = (int64_t)blockIdx.x * RROWS + wave * 16 * TT;
   const int nchunks = Fh / RHC;
 
-  // Weight rings filled by LDS-DMA (global_load_lds_dwordx4 in inline asm, so the compiler adds no
-  // vmcnt(0) before reads of the other slots; the kernel waits for its own pieces explicitly): three
+  // Weight rings filled by LDS-DMA (lds_dma.h: the compiler adds no vmcnt(0) before reads of the
+  // other slots; the kernel waits for its own pieces explicitly): three
   // W1 slots (chunk c+1 read by this chunk's up-projection, c+2 landing, c+3 in flight) and three W2
   // slots (chunk c read, c+1 landing, c+2 in flight), so every fill has two chunks to arrive.  Images
   // are unpadded with 16-B units XOR-swizzled for conflict-free ds_read_b128 fragment reads:
@@ -159,14 +132,14 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : (TT == 2 ? 2 : 1)) void mlp_
     const HT* base = W1 + (int64_t)c * RHC * RE;
 #pragma unroll
     for (int j = 0; j < MP; ++j)
-      mlp_dma16(o1[j], base, __builtin_amdgcn_readfirstlane(lds0 + slot * SLOT_B + (wg * MP + j) * 1024));
+      lds_dma16(o1[j], base, __builtin_amdgcn_readfirstlane(lds0 + slot * SLOT_B + (wg * MP + j) * 1024));
   };
   auto dma_w2 = [&](int c, int slot) {  // W2 columns c*32 .. +31 (permuted), all 192 rows
     if (!gw2) return;
     const HT* base = W2p + c * RHC;
 #pragma unroll
     for (int j = 0; j < MP; ++j)
-      mlp_dma16(o2[j], base,
+      lds_dma16(o2[j], base,
                 __builtin_amdgcn_readfirstlane(lds0 + W2RING + slot * SLOT_B + (wg * MP + j) * 1024));
   };
   // fragment read offsets (bytes inside a slot): W1 row 16 ht + fr, unit 4 ks + fg; W2 row 16 o + fr, unit fg
@@ -236,7 +209,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : (TT == 2 ? 2 : 1)) void mlp_
         if (NW == 4 || (wave >> 2) == hf)  // NW 8: waves 0-3 half 0, 4-7 half 1
 #pragma unroll
           for (int j = 0; j < 9; ++j)
-            mlp_dma16(ow[j], Wout + hf * 96 * RE,
+            lds_dma16(ow[j], Wout + hf * 96 * RE,
                       __builtin_amdgcn_readfirstlane(lds0 + hf * 3 * SLOT_B + (wg * 9 + j) * 1024));
         if (hf == 0) {
           X8 ao[TT][RE / 32];
@@ -262,7 +235,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : (TT == 2 ? 2 : 1)) void mlp_
           const X8 w = *(const X8*)(ldsb + HF * 3 * SLOT_B + fl * 16 * 384 + (ks >> 1) * 128 +
                                     ((ks & 1) ? f1o : f1e));
 #pragma unroll
-          for (int tt = 0; tt < TT; ++tt) y[6 * HF + fl][tt] = mfma16(w, af[tt][ks], y[6 * HF + fl][tt]);
+          for (int tt = 0; tt < TT; ++tt) y[6 * HF + fl][tt] = mfma16x(w, af[tt][ks], y[6 * HF + fl][tt]);
         }
     };
     wait_vm(integral_constant<int, 9>{});  // half 0 (and O, X) landed; half 1 may fly
@@ -412,7 +385,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : (TT == 2 ? 2 : 1)) void mlp_
 #pragma unroll
       for (int ht = 0; ht < 2; ++ht)
 #pragma unroll
-        for (int tt = 0; tt < TT; ++tt) h[ht][tt] = mfma16(wa[ks % PU][ht], af[tt][ks], h[ht][tt]);
+        for (int tt = 0; tt < TT; ++tt) h[ht][tt] = mfma16x(wa[ks % PU][ht], af[tt][ks], h[ht][tt]);
       if (ks + PU < RE / 32)
 #pragma unroll
         for (int ht = 0; ht < 2; ++ht) wa[ks % PU][ht] = w1frag(ht, ks + PU);
@@ -476,7 +449,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : (TT == 2 ? 2 : 1)) void mlp_
       for (int o = 0; o < RE / 16; ++o) {
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int tt = 0; tt < TT; ++tt) y[o][tt] = mfma16(wb[o % PF], hb[tt], y[o][tt]);
+        for (int tt = 0; tt < TT; ++tt) y[o][tt] = mfma16x(wb[o % PF], hb[tt], y[o][tt]);
         if (o + PF < RE / 16) wb[o % PF] = w2frag(o + PF);
       }
     }

@@ -16,25 +16,24 @@
 //     embedding sum + LayerNorm, and small residual / gather / cast helpers.
 #include "common.h"
 #include "modality.h"
+#include "tile_ring.h"
 
 namespace mmpfn {
 
 namespace {
 
 // ---------------------------------------------------------------- big-tile GEMM (bf16)
-constexpr int TM = 256, TN = 256, TK = 32;
-constexpr int TROW = TK * 2;                    // 64-B LDS rows
-constexpr int TSTAGE = (TM + TN) * TROW;        // 32 KB per ring stage
+constexpr int TM = 256, TN = 256;
+static_assert(TM + TN == RING_ROWS, "one ring stage (tile_ring.h)");
 #ifndef GT_NST
 #define GT_NST 4  // 5 (all 160 KB of LDS): ViT batch 20.52-20.55 vs 20.21 ms, profiles/r04/modality/ab_gemm_tile_variants.txt
 #endif
 constexpr int TNST = GT_NST;                    // ring stages (4 x 32 KB: two slices in flight)
-constexpr int TDMA = (TM + TN) * (TROW / 16) / 512;  // 16-B DMA pieces per thread and slice (4)
 constexpr int TMT = TM / 32;                    // 16-row MFMA tiles per wave (8)
 constexpr int OST16 = TN + 8;                   // bf16 output staging row stride (elements)
 constexpr int OST32 = TN + 4;                   // fp32 output staging row stride (floats), 128 rows per pass
 constexpr int imax3(int a, int b, int c) { return a > b ? (a > c ? a : c) : (b > c ? b : c); }
-constexpr int GT_LDS = imax3(TNST * TSTAGE, TM * OST16 * 2, (TM / 2) * OST32 * 4);
+constexpr int GT_LDS = imax3(TNST * RING_STAGE, TM * OST16 * 2, (TM / 2) * OST32 * 4);
 
 #ifndef GT_GM
 #define GT_GM 4  // super-tile (M tiles x N tiles) of the block order
@@ -43,24 +42,9 @@ constexpr int GT_LDS = imax3(TNST * TSTAGE, TM * OST16 * 2, (TM / 2) * OST32 * 4
 #define GT_GN 8
 #endif
 
-__device__ __forceinline__ int gt_slot(int r, int c) { return c ^ ((r >> 1) & 3); }
-
-// "m0" in the clobber list: clang keeps m0 reserved and ignores the entry (-Winline-asm; the ISA is identical with
-// and without it), and every m0 use the compiler emits itself is preceded by its own write -- test_codegen checks
-// that no m0 read other than these DMA issues exists in the kernels
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-__device__ __forceinline__ void gt_dma16(const void* src, unsigned lds_base) {
-  // m0 = the wave's LDS destination; lane i's 16 B land at m0 + 16 i
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(lds_base) : "memory", "m0");
-}
-#pragma clang diagnostic pop
-
 // C = A[M][K] . W[N][K]^T, 256 x 256 tile per 512-thread block (8 waves as 2 x 4, each 128 x 64 =
-// 8 x 4 MFMA-16 tiles).  K moves in 32-wide slices through a 4-stage LDS ring filled by LDS-DMA
-// (slice kt+1..kt+3 in flight while kt computes, one barrier per slice); LDS rows are unpadded 64 B
-// with 16-B chunk c of row r at slot c ^ ((r >> 1) & 3) (conflict-free ds_read_b128).  Blocks are
-// ordered so one XCD runs all M tiles of a W tile back to back (W tile fetched ~once per L2).
+// 8 x 4 MFMA-16 tiles).  K moves in 32-wide slices through the 4-stage LDS ring of tile_ring.h (slices
+// kt+1..kt+3 in flight while kt computes).  Blocks are ordered in super-tiles per XCD (below).
 template <int EPI, int ACT>
 __global__ __launch_bounds__(512, 1) void gemm_tile_kernel(const bf16* __restrict__ A, const bf16* __restrict__ W,
                                                            const float* __restrict__ bias,
@@ -77,10 +61,8 @@ __global__ __launch_bounds__(512, 1) void gemm_tile_kernel(const bf16* __restric
   // order would stream every A panel once per N tile).
   int mt, nt;
   {
-    const int nb = gridDim.x, ntiles = nb / mtiles;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int per = nb >> 3, extra = nb & 7;
-    const int t = xcd * per + min(xcd, extra) + slot;
+    const int ntiles = gridDim.x / mtiles;
+    const int t = xcd_task(blockIdx.x, gridDim.x);
     const int gn = min(GT_GN, ntiles);
     const int c = min(t / (mtiles * gn), (ntiles - 1) / gn);  // N chunk
     const int w = min(gn, ntiles - c * gn);                     // its width
@@ -92,17 +74,14 @@ __global__ __launch_bounds__(512, 1) void gemm_tile_kernel(const bf16* __restric
   const int m0 = mt * TM, n0 = nt * TN;
   const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)smem;
 
-  const bf16* src[TDMA];
+  const bf16* src[RING_DMA];
 #pragma unroll
-  for (int j = 0; j < TDMA; ++j) {
-    const int q = (wave * TDMA + j) * 64 + lane, r = q >> 2, c = gt_slot(r, q & 3);
+  for (int j = 0; j < RING_DMA; ++j) {
+    int r, c;
+    ring_piece(wave, lane, j, r, c);
     src[j] = r < TM ? A + (int64_t)min(m0 + r, M - 1) * K + c * 8 : W + (int64_t)(n0 + r - TM) * K + c * 8;
   }
-  auto dma = [&](int kt) {
-    const unsigned base = lds0 + (kt % TNST) * TSTAGE + wave * TDMA * 1024;
-#pragma unroll
-    for (int j = 0; j < TDMA; ++j) gt_dma16(src[j] + kt * TK, __builtin_amdgcn_readfirstlane(base + j * 1024));
-  };
+  auto dma = [&](int kt) { ring_issue<TNST>(src, kt, lds0, wave); };
   f32x4 acc[TMT][4];
 #pragma unroll
   for (int a = 0; a < TMT; ++a)
@@ -117,32 +96,27 @@ __global__ __launch_bounds__(512, 1) void gemm_tile_kernel(const bf16* __restric
   // DMA: slice s >= TNST is issued in phase 2(s - TNST) + 2 (its stage was last read, by group 1, in
   // phase 2(s - TNST) + 1); each wave waits for its own pieces of slice j before the barrier that
   // ends phase 2j - 1, so slice j is complete and visible when group 0 reads it in phase 2j.
-  const int nk = K / TK;
+  const int nk = K / RING_K;
 #pragma unroll
   for (int i = 0; i < TNST; ++i)
     if (i < nk) dma(i);
-  {  // slice 0 visible before phase 0
-    const int c = min(nk - 1, TNST - 1);
-    if (c >= 4) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * TDMA) : "memory");
-    else if (c == 3) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * TDMA) : "memory");
-    else if (c == 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * TDMA) : "memory");
-    else if (c == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(TDMA) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
+  ring_wait<TNST - 1>(min(nk - 1, TNST - 1));  // slice 0 visible before phase 0: every later slice may still fly
   __syncthreads();
   bf16x8 af[TMT], bw[4];
+  // ring_read<TM> (tile_ring.h) kept written out: through the helper this kernel allocates 190 VGPRs for 192 and
+  // its prologue arithmetic changes (profiles/r09)
   auto read = [&](int j) {
-    const unsigned char* As = smem + (j % TNST) * TSTAGE;
-    const unsigned char* Ws = As + TM * TROW;
+    const unsigned char* As = smem + (j % TNST) * RING_STAGE;
+    const unsigned char* Ws = As + TM * RING_ROW;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int rb = wn * 64 + i * 16 + fr;
-      bw[i] = *(const bf16x8*)(Ws + rb * TROW + 16 * gt_slot(rb, fg));
+      bw[i] = *(const bf16x8*)(Ws + rb * RING_ROW + 16 * swz64(rb, fg));
     }
 #pragma unroll
     for (int i = 0; i < TMT; ++i) {
       const int ra = wm * (TM / 2) + i * 16 + fr;
-      af[i] = *(const bf16x8*)(As + ra * TROW + 16 * gt_slot(ra, fg));
+      af[i] = *(const bf16x8*)(As + ra * RING_ROW + 16 * swz64(ra, fg));
     }
   };
   auto compute = [&]() {
@@ -150,7 +124,7 @@ __global__ __launch_bounds__(512, 1) void gemm_tile_kernel(const bf16* __restric
 #pragma unroll
     for (int a = 0; a < TMT; ++a)
 #pragma unroll
-      for (int b = 0; b < 4; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[a], bw[b], acc[a][b], 0, 0, 0);
+      for (int b = 0; b < 4; ++b) acc[a][b] = mfma16x(af[a], bw[b], acc[a][b]);
     __builtin_amdgcn_s_setprio(0);
   };
   auto issue = [&](int p) {  // even phase p >= 2 issues slice p/2 - 1 + TNST
@@ -159,11 +133,7 @@ __global__ __launch_bounds__(512, 1) void gemm_tile_kernel(const bf16* __restric
   };
   auto wait_for = [&](int j) {  // end of phase 2j - 1: own pieces of slice j landed
     if (j >= nk) return;
-    const int c = min(nk - 1, j + TNST - 2) - j;
-    if (c >= 3) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * TDMA) : "memory");
-    else if (c == 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * TDMA) : "memory");
-    else if (c == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(TDMA) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    ring_wait<TNST - 2>(min(nk - 1, j + TNST - 2) - j);
   };
   if (wm == 0) {  // phases 2j: read j | 2j+1: compute j | 2nk: idle
     for (int j = 0; j < nk; ++j) {
@@ -294,8 +264,7 @@ __global__ __launch_bounds__(256, 2) void attn64_kernel(const bf16* __restrict__
   const int64_t ld = 3 * (int64_t)D;
   int b, h, chunk;
   {  // XCD-contiguous task ranges: the blocks of one (b, h) share an L2
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int task = xcd * (nblocks >> 3) + min(xcd, nblocks & 7) + slot;
+    const int task = xcd_task(blockIdx.x, nblocks);
     chunk = task % chunks;
     const int bh = task / chunks;
     h = bh % H, b = bh / H;
@@ -840,7 +809,7 @@ hipError_t launch_gemm_tile(const void* A, const void* W, const float* bias, con
                             int64_t ldc, int M, int N, int K, int epi, int act, hipStream_t st) {
   if (M <= 0) return hipSuccess;
   // act outside 0 / 1 would alias another epilogue's case below (GT_BF16 with act 2 is GT_RESID * 2)
-  if (N % TN != 0 || K % TK != 0 || K <= 0 || act < 0 || act > 1 || (epi != GT_BF16 && act != 0))
+  if (N % TN != 0 || K % RING_K != 0 || K <= 0 || act < 0 || act > 1 || (epi != GT_BF16 && act != 0))
     return hipErrorInvalidValue;
   const int mtiles = (M + TM - 1) / TM;
   const int64_t nb = (int64_t)mtiles * (N / TN);

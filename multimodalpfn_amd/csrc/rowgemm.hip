@@ -29,13 +29,6 @@ constexpr int GROWS = 128;      // rows per block
 constexpr int WST = GE + 16;    // LDS panel row stride (bf16): 416 B
 constexpr int WPC = GE * GE / 8 / 256;  // 16-B panel pieces per thread (18)
 
-__device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x4 mfma16(f16x8 a, f16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-
 struct RgArgs {
   const void* A;     // fp32 / fp16 (F16) rows (QKV) or 16-bit rows (RES_LN), ld = 192
   int64_t a_rdiv, a_rmul, a_rmul2, a_roff;  // logical row m -> memory row (m/rdiv)*rmul + (m%rdiv)*rmul2 + roff
@@ -125,9 +118,9 @@ __device__ __forceinline__ void panel_mma(const uint16_t* Ws, const X8 (&af)[2][
 #pragma unroll
       for (int tt = 0; tt < 2; ++tt) {
         if constexpr (TRANS)
-          acc[g * 4 + i][tt] = mfma16(w[it & 1][i], af[tt][ks], acc[g * 4 + i][tt]);
+          acc[g * 4 + i][tt] = mfma16x(w[it & 1][i], af[tt][ks], acc[g * 4 + i][tt]);
         else
-          acc[g * 4 + i][tt] = mfma16(af[tt][ks], w[it & 1][i], acc[g * 4 + i][tt]);
+          acc[g * 4 + i][tt] = mfma16x(af[tt][ks], w[it & 1][i], acc[g * 4 + i][tt]);
       }
   }
 }
@@ -159,9 +152,9 @@ __device__ __forceinline__ void chunk_mma(const uint16_t* W, const X8 (&af)[2][G
 #pragma unroll
       for (int tt = 0; tt < 2; ++tt) {
         if constexpr (TRANS)
-          acc[f][tt] = mfma16(w[ks & 1][f], af[tt][ks], acc[f][tt]);
+          acc[f][tt] = mfma16x(w[ks & 1][f], af[tt][ks], acc[f][tt]);
         else
-          acc[f][tt] = mfma16(af[tt][ks], w[ks & 1][f], acc[f][tt]);
+          acc[f][tt] = mfma16x(af[tt][ks], w[ks & 1][f], acc[f][tt]);
       }
   }
 }

@@ -29,10 +29,6 @@ constexpr int P3TILE = 32;             // rows per wave tile
 constexpr int P3W = 8;                 // waves per block (two per SIMD)
 constexpr int P3D = 3;                 // W fragment slots read ahead of their MFMAs
 
-__device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-
 struct P3Set {
   const float* A;
   int a_rdiv, a_rmul, a_rmul2, a_roff;
@@ -87,6 +83,8 @@ __device__ __forceinline__ void load_rows3(const P3Set& ps, int t, int fr, int f
   }
 }
 
+// the same rule as split_bf16 (common.h), kept written out element by element: through split_bf16 proj3_kernel's
+// register allocation changes (profiles/r09)
 __device__ __forceinline__ void split_rows3(const f32x4 (&raw)[2][P3KS][2], bf16x8 (&ah)[2][P3KS],
                                             bf16x8 (&al)[2][P3KS]) {
 #pragma unroll
@@ -135,17 +133,17 @@ __device__ __forceinline__ void mma3(const bf16* wl, const bf16x8 (&ah)[2][P3KS]
 #pragma unroll
       for (int e = 0; e < 2; ++e)
 #pragma unroll
-        for (int tt = 0; tt < 2; ++tt) acc[f0 + e][tt] = mfma16(w[e], ah[tt][ks], acc[f0 + e][tt]);
+        for (int tt = 0; tt < 2; ++tt) acc[f0 + e][tt] = mfma16x(w[e], ah[tt][ks], acc[f0 + e][tt]);
     } else {
 #pragma unroll
       for (int e = 0; e < 2; ++e)
 #pragma unroll
-        for (int tt = 0; tt < 2; ++tt) acc[f0 + e][tt] = mfma16(w[e], al[tt][ks], acc[f0 + e][tt]);
+        for (int tt = 0; tt < 2; ++tt) acc[f0 + e][tt] = mfma16x(w[e], al[tt][ks], acc[f0 + e][tt]);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int e = 0; e < 2; ++e)
 #pragma unroll
-        for (int tt = 0; tt < 2; ++tt) acc[f0 + e][tt] = mfma16(w[e], ah[tt][ks], acc[f0 + e][tt]);
+        for (int tt = 0; tt < 2; ++tt) acc[f0 + e][tt] = mfma16x(w[e], ah[tt][ks], acc[f0 + e][tt]);
     }
   }
 }

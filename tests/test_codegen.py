@@ -151,6 +151,13 @@ def test_product_sources_carry_no_ablation_switches():
         assert not hits, (src.name, sorted(set(hits)))
 
 
+def test_lds_dma_issue_has_one_definition():
+    """The LDS-DMA inline asm and its m0 / vmcnt contract are written once (lds_dma.h)."""
+    hits = [src.name for src in sorted(CSRC.iterdir()) if src.is_file() and src.suffix in (".hip", ".cpp", ".h")
+            and "global_load_lds_dwordx4" in src.read_text()]
+    assert hits == ["lds_dma.h"], hits
+
+
 def test_shipped_library_is_the_production_build():
     """Variant builds export ``mmpfn_variant_flags`` (tools/build_variant*.sh, make dbg) and the loader
     refuses them without MMPFN_DIAGNOSTICS=1; the in-tree library must not carry the marker."""

@@ -4,7 +4,9 @@ then  python tools/lib_outputs.py --compare a.npz b.npz
 Legs: the fp16, bf16, fp32 (split-bf16) and fp32-MFMA logits of every golden case; the two fp16 + fp8 P.V modes on
 pad_ufes_12l, and its four base modes with the last layer run in full; forward_many with 2 lanes and batch 2 on one
 golden; a table wider than 64 tokens per row (the bf16 fallback path) in the bf16, fp32 and fp32-MFMA modes: the
-forward, the cached predict, and the layer-0 attention taps; and the four C-ABI item-attention taps on a seeded case."""
+forward, the cached predict, and the layer-0 attention taps, and that model's MGM bank and mixer tokens in the fp16 and
+bf16 modes (the big-tile mixer GEMMs); the four C-ABI item-attention taps on a seeded case; and the modality towers'
+GEMM (mmpfn_enc_linear) with each epilogue."""
 import sys
 from pathlib import Path
 
@@ -75,8 +77,41 @@ def wide_legs(_lib):
             cache.free()
             res[f"wide_feat_tap_{name}"] = eng.feature_attention(0, X, p)
             res[f"wide_item_tap_{name}"] = eng.item_attention_block(0, X, N, p)
+        # the big-tile mixer GEMMs (gemm_glu_big_kernel, gemm_remap_big_kernel), S = 330: two M tiles of 256, one
+        # full and one partial tile of 320; mixer_tokens of this MGM + CAP model takes the 16-bit token output
+        im = torch.randn(330, 2, cfg.nhid, generator=torch.Generator().manual_seed(23)).cuda()
+        for name, p in (("f16", _lib.PREC_F16), ("bf16", _lib.PREC_BF16)):
+            res[f"mgm_{name}"] = eng.mgm(im, p)
+            res[f"mixer_tokens_{name}"] = eng.mixer_tokens(im, p)
         eng.status()
     return {k: v.cpu().numpy() for k, v in res.items()}
+
+
+def enc_linear_legs(_lib):
+    """mmpfn_enc_linear (gemm_tile_kernel), M = 300 (two M tiles, the second partial), N = 512: K = 256 (eight
+    slices: the four-stage ring wraps) and K = 64 (two slices, fewer than the stages), each epilogue."""
+    import modality_kernel_cases as mk
+    import torch
+
+    lib = _lib.load_library()
+    enc = lib.mmpfn_enc_create(0, None)
+    assert enc
+    M, N = 300, 512
+    res = {}
+    for K in (256, 64):
+        ops = mk.operands(M, N, K, "normal", seed=K)
+        A, W, bias, gamma = (ops[k].cuda() for k in ("A", "W", "bias", "gamma"))
+        for name, epi, act in (("bf16", mk.EPI_BF16, 0), ("bf16_gelu", mk.EPI_BF16, 1), ("f32", mk.EPI_F32, 0),
+                               ("resid", mk.EPI_RESID, 0)):
+            C = ops["c0"].cuda() if epi == mk.EPI_RESID else torch.zeros(
+                M, N, device="cuda", dtype=torch.bfloat16 if epi == mk.EPI_BF16 else torch.float32)
+            rc = lib.mmpfn_enc_linear(enc, A.data_ptr(), W.data_ptr(), bias.data_ptr(),
+                                      gamma.data_ptr() if epi == mk.EPI_RESID else None, C.data_ptr(), M, N, K, epi, act)
+            assert rc == 0, (K, name, rc)
+            torch.cuda.synchronize()
+            res[f"enc_linear_K{K}_{name}"] = C.float().cpu().numpy()
+    lib.mmpfn_enc_destroy(enc)
+    return res
 
 
 def attention_tap_legs(_lib):
@@ -138,6 +173,7 @@ def main():
             model.engine().full_last_layer = False
     res.update(wide_legs(_lib))
     res.update(attention_tap_legs(_lib))
+    res.update(enc_linear_legs(_lib))
     np.savez(sys.argv[1], **res)
     print("saved", len(res), "outputs to", sys.argv[1])
 
