@@ -39,6 +39,9 @@
  *   mmpfn_outproj_mlp_ln
  *       <- model/layer.py:341-379's out-projection with its post-norm, then :410-424 with its own (:437-455):
  *          what follows the item attention's softmax(QK^T)V in one PerFeatureEncoderLayer
+ *   mmpfn_item_qkv
+ *       <- model/layer.py:341-372's q / k / v projections, train rows (:362-372) and test rows (:344-358):
+ *          what precedes the item attention's softmax(QK^T)V
  *   mmpfn_mgm / mmpfn_cap
  *       <- model/transformer.py:33-57 MultiheadGatedMLP / :60-88 CrossAttentionPooler
  */
@@ -327,9 +330,33 @@ int mmpfn_mlp_ln(mmpfn_ctx* ctx, int layer, float* X, int64_t rows, int precisio
  *                               which no 16-bit forward launches; fp32: the forwards' kernels.
  *   mmpfn_mlp_ln                16-bit: mlp_rows_kernel without the prologue (RES = false), which no 16-bit forward
  *                               launches; fp32: the forwards' kernel.
+ *   mmpfn_item_qkv (below)      every mode: the forwards' projection kernel(s), through the host function the forwards
+ *                               share with it -- 16-bit rowgemm_qkv2_kernel, MMPFN_PREC_F32 proj3_kernel,
+ *                               MMPFN_PREC_F32_MFMA gemm_kernel with the EPI_ITEM_QKV epilogue.
  * MMPFN_ERR_INVALID (mmpfn_last_error says which) for rows <= 0, a null O, a layer outside [0, nlayers) or an
  * unknown precision; nothing is launched then. */
 int mmpfn_outproj_mlp_ln(mmpfn_ctx* ctx, int layer, float* X, const void* O, int64_t rows, int precision);
+/* The item attention's projection alone, through the host function the forwards' layers call.
+ * X: device [M][T][S][E] fp32, not modified.  N > 0: rows [0, N) through q|k|v, rows [N, S) through the test rows' q
+ * (N == S: no test rows, a cache build's form).  N == 0: the train-KV cache's predict form, all S rows through the test
+ * rows' q; k / vt unused and may be null.  last != 0: the pruned last layer's form, column T-1 of every member only.
+ * q [TM][H][S][32], k [TM][H][Npad][32], vt [TM][H][32][Npad], TM = last ? M : M * T, Npad = ceil(N / 64) * 64, in
+ * the mode's operand type (fp32: MMPFN_PREC_F32 / _F32_MFMA; bf16: every 16-bit code), written in place into the
+ * caller's buffers: what the kernels do not store stays as the caller left it -- K rows and V^T columns [N, Npad), and
+ * all of k / vt when N == 0.  The 16-bit modes' q comes out times log2(e) / sqrt(32), as their attention kernel takes it
+ * (q_prescaled); the fp32 modes' q is the plain projection.  The precision is decoded as mmpfn_item_attention_block
+ * decodes it: MMPFN_PREC_F16* at T > 64 runs as MMPFN_PREC_BF16*, and the fp8 codes run their base mode's projection.
+ * MMPFN_PREC_F16* projects an fp16 copy of X held by the context.
+ * Which kernel runs, by mode:
+ *   MMPFN_PREC_BF16*, _F16*   rowgemm_qkv2_kernel: both row sets in one launch, 128-row blocks per column, the test
+ *                             rows' q-only blocks last.
+ *   MMPFN_PREC_F32            proj3_kernel (split-bf16 products): both sets in one launch, 32-row tiles over all rows.
+ *   MMPFN_PREC_F32_MFMA       gemm_kernel with the EPI_ITEM_QKV epilogue, one launch per non-empty row set.
+ * MMPFN_ERR_INVALID (mmpfn_last_error says which) for S <= 0, T <= 0, M <= 0, N < 0, N > S, a null q, a null k or vt
+ * with N > 0, a layer outside [0, nlayers) or an unknown precision; a null ctx or X returns it without a message;
+ * nothing is launched then. */
+int mmpfn_item_qkv(mmpfn_ctx* ctx, int layer, const float* X, int S, int T, int N, int M, int last, int precision,
+                   void* q, void* k, void* vt);
 /* modality heads: image [S][n_mod][nhid] -> MGM tokens [S][mgm*n_mod][E] (head-major, as the
  * reference concatenates them); MGM tokens [S][M][E] -> CAP tokens [S][cap][E] */
 int mmpfn_mgm(mmpfn_ctx* ctx, const float* image, int S, int n_mod, float* tokens, int precision);

@@ -515,8 +515,33 @@ int feat_sublayer(mmpfn_ctx* ctx, const LayerW& L, void* Xv, int S, int T, int M
   return MMPFN_OK;
 }
 
-// ---- attention between items (layer.py:341-379) of layer l; rows of all members: logical row
-//      (member*T + t)*N + n -> memory row (member*T + t)*S + n, attention batch member*T + t.
+// ---- the item attention's q|k|v projection of layer l: the one place that builds its row sets.  Rows of all members:
+//      logical row (member*T + t)*N + n -> memory row (member*T + t)*S + n, attention batch member*T + t.
+//      Not cached: the train rows [0, N) through q|k|v and the test rows [N, S) through the test rows' q, in one launch
+//      where the mode has one (test-row blocks last; an empty test set launches no block: its M is 0 whatever its
+//      divisor).  cached (a predict against a train-KV cache): every one of the S rows through the test rows' q; K / Vt
+//      are not written.  last: the pruned last layer's form, the target-token column T-1 of every member only -- M
+//      columns, T*S state rows apart, into compact Q [M][H][S][32], K [M][H][Npad][32], V^T [M][H][32][Npad].
+//      item_sublayer and the mmpfn_item_qkv tap both come here: what the tap runs is what the forwards run.
+int item_project(mmpfn_ctx* ctx, int l, const void* Xv, int S, int T, int N, int Npad, int M, PrecMode pm, bool last,
+                 bool cached, void* Q, void* K, void* Vt) {
+  const LayerW& L = ctx->w.layers[l];
+  const int E = ctx->d.emsize, H = ctx->d.nhead;
+  const int TM = last ? M : T * M;               // token columns of the batch (attention batches)
+  const int64_t cs = last ? (int64_t)T * S : S;  // state rows between consecutive columns
+  if (last) Xv = (const char*)Xv + (size_t)(T - 1) * S * E * pm.state_bytes();
+  if (cached) {
+    const QkvRows rows{L.item_qtest, {S, cs, 1, 0, TM * S, E}};
+    return project_qkv(ctx, pm, true, Xv, &rows, 1, Q, K, Vt, S, Npad, H);
+  }
+  const int nq = S - N;
+  const QkvRows rows[2] = {{L.item_qkv, {N, cs, 1, 0, TM * N, 3 * E}},
+                           {L.item_qtest, {nq > 0 ? nq : 1, cs, 1, N, TM * nq, E}}};
+  return project_qkv(ctx, pm, true, Xv, rows, 2, Q, K, Vt, S, Npad, H);
+}
+
+// ---- attention between items (layer.py:341-379) of layer l over the rows of all members (item_project has the row
+//      map).
 //      fuse_out: the out-projection + residual + LN is left to the caller's layer_tail (the attention output
 //      stays in ws_O; the 16-bit modes run it as the MLP kernel's prologue); otherwise -- the
 //      mmpfn_item_attention_block tap -- X <- LN(X + O Wout^T) here.
@@ -530,11 +555,9 @@ int item_sublayer(mmpfn_ctx* ctx, int l, void* Xv, int S, int T, int N, int Npad
   const mmpfn_model_desc& d = ctx->d;
   const LayerW& L = ctx->w.layers[l];
   const int E = d.emsize, H = d.nhead, Q = S - N;
-  const int TM = last ? M : T * M;               // token columns of the batch (attention batches)
-  const int64_t RM = (int64_t)S * TM;            // tokens of the batch
-  const int64_t cs = last ? (int64_t)T * S : S;  // state rows between consecutive columns
+  const int TM = last ? M : T * M;     // token columns of the batch (attention batches)
+  const int64_t RM = (int64_t)S * TM;  // tokens of the batch
   const int c0 = last ? T - 1 : 0, nc = last ? 1 : T;  // the columns of one member, as the cache numbers them
-  if (last) Xv = (char*)Xv + (size_t)(T - 1) * S * E * pm.state_bytes();
   const int eb = pm.op_bytes();
   hipStream_t st = ctx->stream;
   void* O = ctx->ws_O.p;
@@ -542,23 +565,18 @@ int item_sublayer(mmpfn_ctx* ctx, int l, void* Xv, int S, int T, int N, int Npad
   void* Qi = big;
   void* Ki = big + (size_t)RM * E * eb;
   void* Vi = (unsigned char*)Ki + (size_t)TM * H * Npad * 32 * eb;
+  RC(item_project(ctx, l, Xv, S, T, N, Npad, M, pm, last, ctx->cache_in != nullptr, Qi, Ki, Vi));
   if (ctx->cache_in) {  // every row is a test row: Q only, against the cached train K/V of head 0
     const mmpfn_cache* cc = ctx->cache_in;
     const size_t kvl = (size_t)T * cc->Npad * 32 * eb;
     const size_t ccol = (size_t)c0 * cc->Npad * 32 * eb;  // the first column's K (V^T) block inside the layer's
     const unsigned char* Kc = (const unsigned char*)cc->kv.p + (size_t)l * 2 * kvl + ccol;
-    const QkvRows rows{L.item_qtest, {S, cs, 1, 0, TM * S, E}};
-    RC(project_qkv(ctx, pm, true, Xv, &rows, 1, Qi, Ki, Vi, S, Npad, H));
     AttnLayerArgs a{Qi, Kc, Kc + kvl, O, S, TM, H, cc->Npad, cc->N};
     a.a0 = 0, a.na = 0, a.b0 = 0, a.nb = S, a.kvb = 0;  // every row against head 0 of the cache
     a.kv_bstride = (int64_t)cc->Npad * 32;
     a.q_prescaled = pm.is16(), a.qk_t = pm.qk(), a.o_t = pm.attn_out();
     HIPCHK(launch_attn_layer(a, pm.base, st));
   } else {
-    // train rows q|k|v and test rows q in one launch where the mode has one (test-row blocks last)
-    const QkvRows rows[2] = {{L.item_qkv, {N, cs, 1, 0, TM * N, 3 * E}},
-                             {L.item_qtest, {Q > 0 ? Q : 1, cs, 1, N, TM * Q, E}}};
-    RC(project_qkv(ctx, pm, true, Xv, rows, 2, Qi, Ki, Vi, S, Npad, H));
     if (ctx->cache_out) {  // keep head 0's K / V^T of every column (the test rows' KV, layer.py:344-358)
       mmpfn_cache* cc = ctx->cache_out;
       const size_t blk = (size_t)Npad * 32 * eb, kvl = (size_t)T * blk;
@@ -875,6 +893,14 @@ int state_tap(mmpfn_ctx* ctx, float* X, int64_t n, PrecMode pm, F&& run) {
   RC(run(ctx->tap_x16.p));
   HIPCHK(launch_f16_to_f32(ctx->tap_x16.p, 0, X, 0, n, 1, ctx->stream));
   return MMPFN_OK;
+}
+// the same for a tap that only reads the state: nothing is converted back, the caller's X is left alone
+template <typename F>
+int state_tap_ro(mmpfn_ctx* ctx, const float* X, int64_t n, PrecMode pm, F&& run) {
+  if (!pm.f16()) return run((const void*)X);
+  RC(ensure(ctx, ctx->tap_x16, (size_t)n * 2));
+  HIPCHK(launch_f32_to_f16(X, 0, ctx->tap_x16.p, 0, n, 1, ctx->stream));
+  return run((const void*)ctx->tap_x16.p);
 }
 
 }  // namespace
@@ -1319,6 +1345,19 @@ int mmpfn_item_attention_block(mmpfn_ctx* ctx, int layer, float* X, int S, int T
   const PrecMode pm = decode_prec(precision, T);
   return state_tap(ctx, X, (int64_t)S * T * ctx->d.emsize, pm, [&](void* Xs) {
     return item_sublayer(ctx, layer, Xs, S, T, N, Npad, 1, pm, false);
+  });
+}
+
+int mmpfn_item_qkv(mmpfn_ctx* ctx, int layer, const float* X, int S, int T, int N, int M, int last, int precision,
+                   void* q, void* k, void* vt) {
+  RC(tap_check(ctx, layer, X, precision));
+  if (S <= 0 || T <= 0 || N < 0 || N > S) return fail(ctx, MMPFN_ERR_INVALID, "bad state geometry");
+  if (M <= 0) return fail(ctx, MMPFN_ERR_INVALID, "bad member count");
+  if (!q || (N > 0 && (!k || !vt))) return fail(ctx, MMPFN_ERR_INVALID, "null projection output");
+  const int Npad = (N + 63) / 64 * 64;
+  const PrecMode pm = decode_prec(precision, T);
+  return state_tap_ro(ctx, X, (int64_t)M * S * T * ctx->d.emsize, pm, [&](const void* Xs) {
+    return item_project(ctx, layer, Xs, S, T, N, Npad, M, pm, last != 0, N == 0, q, k, vt);
   });
 }
 

@@ -635,6 +635,32 @@ class HipEngine:
                     "mmpfn_outproj_mlp_ln")
         return Xd
 
+    def item_qkv(self, layer: int, X: torch.Tensor, n_train: int, precision: int, last: bool = False,
+                 fill: torch.Tensor | None = None):
+        """The item attention's projection alone through ``mmpfn_item_qkv``: ``X`` ``[M, S, T, E]`` (each member in
+        reference order) -> ``(q [TM, H, S, 32], k [TM, H, Npad, 32], vt [TM, H, 32, Npad])`` in the mode's operand
+        type (fp32 in the fp32 modes, bf16 in every 16-bit one), TM = M if ``last`` (column T - 1 only) else M * T,
+        Npad = n_train rounded up to 64.  ``n_train == 0``: the train-KV cache's predict form, q of all S rows through
+        the test rows' weights; k and vt come back empty.  ``fill``: a one-element tensor of the operand type that the
+        outputs are pre-filled with (what the kernels do not store keeps it); without it they are zero-filled."""
+        Xd = self._dev(X)
+        if Xd.dim() != 4:
+            raise ValueError(f"X must be [M, S, T, E], got {tuple(Xd.shape)}")
+        Xt = Xd.transpose(1, 2).contiguous()
+        M, T, S, _ = Xt.shape
+        odt = torch.float32 if precision in (_lib.PREC_F32, _lib.PREC_F32_MFMA) else torch.bfloat16
+        TM, H, npad = (M if last else M * T), self.cfg.nhead, (n_train + 63) // 64 * 64
+        q, k, vt = (torch.zeros(shape, dtype=odt, device=Xt.device)
+                    for shape in ((TM, H, S, 32), (TM, H, npad, 32), (TM, H, 32, npad)))
+        if fill is not None:
+            for t in (q, k, vt):
+                t.copy_(fill.to(device=t.device).reshape(()).expand_as(t))
+        self._bind_stream()
+        self._check(self.lib.mmpfn_item_qkv(self.ctx, layer, _ptr(Xt), S, T, n_train, M, int(last), precision,
+                                            _ptr(q), _ptr(k) if n_train else None, _ptr(vt) if n_train else None),
+                    "mmpfn_item_qkv")
+        return q, k, vt
+
     def mgm(self, image, precision: int) -> torch.Tensor:
         """MultiheadGatedMLP tokens ``[S, mgm * n_mod, E]`` (transformer.py:33-57)."""
         img = self._dev(image)
