@@ -31,6 +31,9 @@
  *   mmpfn_bar_head
  *       <- regressor.py:652-706 (temperature, cancel mask, translate_probs_across_borders, ensemble mean) and
  *          :732-765 _logits_to_output on the renormalised FullSupportBarDistribution
+ *   mmpfn_bar_score / mmpfn_bar_head_score
+ *       <- model/bar_distribution.py:487-571 forward (the negative log density), :59-97 cdf, :629-675 pi,
+ *          :677-758 ei, :600-626 mean_of_square of FullSupportBarDistribution; alone, or fused into mmpfn_bar_head
  *   mmpfn_status
  *       <- model/transformer.py:727-731,790-796 NaN checks (ValueError)
  *   mmpfn_feature_attention / mmpfn_item_attention_block / mmpfn_mlp_ln
@@ -193,6 +196,38 @@ int mmpfn_bar_head(mmpfn_ctx* ctx, const float* logits, int M, int Q, int B, con
                    const int* idx, const float* share, int ldt, float inv_temperature, int average_before_softmax,
                    const float* borders, const float* bucket_means, const float* mode_means, const float* widths,
                    const float* levels, int K, float* out_logits, float* mean, float* mode, float* quantiles);
+
+/* Scores of a bar distribution at given targets (the rest of FullSupportBarDistribution, bar_distribution.py:59-97,
+ * 487-571, 600-675, 706-758), always fp32, one block per row:
+ * logits [Q][B] (any: the head's out_logits or one member's; -inf is a bar of weight zero), softmax(logits *
+ *   inv_temperature) as the head's last stage computes it;
+ * borders [B + 1], widths [B] and the score tables, all from FullSupportBarDistribution.score_tables() (what depends
+ *   on the borders alone, float32): log_widths [B]; mean_squares [B] (the per-bucket means of squares, :606-624);
+ *   ei_mids [B] (the interior buckets' plain means minus the border ends[8]; 0 in the two end buckets);
+ *   ends [MMPFN_BAR_SCORE_ENDS]: per end bucket (first, last) the half-normal's scale [0..1], 1 / scale [2..3],
+ *   1 / (2 scale^2) [4..5], its log density at 0 plus the log of the bucket's width [6..7]; [8] the centre of ei_mids;
+ * ys [Q][J] targets on the borders' scale, 0 <= J <= MMPFN_BAR_MAX_TARGETS.
+ * Outputs, each may be NULL: nll [Q][J] the negative log density (forward, :487-571; 0 at a NaN target), cdf (:59-97),
+ * pi (:629-675) and ei (:706-758) with the target as best_f, [Q][J], NaN at a NaN target; mean_of_square [Q]
+ * (:600-626).  The bucket of a target is searchsorted(borders, y) - 1 (left side), clamped.
+ * MMPFN_ERR_INVALID: J or B (2 .. MMPFN_BAR_MAX_BARS) out of range, a per-target output without ys.  Q = 0 is fine. */
+#define MMPFN_BAR_MAX_TARGETS 64
+#define MMPFN_BAR_SCORE_ENDS 9
+int mmpfn_bar_score(mmpfn_ctx* ctx, const float* logits, int Q, int B, float inv_temperature, const float* borders,
+                    const float* widths, const float* log_widths, const float* mean_squares, const float* ei_mids,
+                    const float* ends, const float* ys, int J, float* nll, float* cdf, float* pi, float* ei,
+                    float* mean_of_square);
+
+/* mmpfn_bar_head with the scores of every finished row from the same kernel: mmpfn_bar_head's arguments, then
+ * mmpfn_bar_score's tables (borders and widths are the head's own), targets and outputs.  Every output of
+ * mmpfn_bar_head is bit for bit what that call gives, and the scores are those of mmpfn_bar_score on its out_logits at
+ * inv_temperature 1; out_logits may be NULL, so the [Q][B] log-probabilities need not reach memory. */
+int mmpfn_bar_head_score(mmpfn_ctx* ctx, const float* logits, int M, int Q, int B, const unsigned char* cancel, int ldc,
+                         const int* idx, const float* share, int ldt, float inv_temperature, int average_before_softmax,
+                         const float* borders, const float* bucket_means, const float* mode_means, const float* widths,
+                         const float* levels, int K, float* out_logits, float* mean, float* mode, float* quantiles,
+                         const float* log_widths, const float* mean_squares, const float* ei_mids, const float* ends,
+                         const float* ys, int J, float* nll, float* cdf, float* pi, float* ei, float* mean_of_square);
 
 /* Synchronises the context stream and reports deferred device-side errors
  * (MMPFN_ERR_NAN when the embedded input held NaNs). */

@@ -21,6 +21,7 @@ MMPFN_ERR_NAN = -3
 MMPFN_ERR_STATE = -4
 MMPFN_ERR_WEIGHT = -5
 BAR_MAX_BARS, BAR_MAX_MEMBERS, BAR_MAX_LEVELS = 8192, 1024, 64  # mmpfn_bar_head's limits (MMPFN_BAR_MAX_*)
+BAR_MAX_TARGETS, BAR_SCORE_ENDS = 64, 9  # mmpfn_bar_score's (MMPFN_BAR_MAX_TARGETS, MMPFN_BAR_SCORE_ENDS)
 
 PREC_F32 = 0       # parity mode: split-bf16 three-product MFMAs (fp32 operands to 2^-16), fp32 softmax / LN
 PREC_BF16 = 1      # 16-bit mode with bf16 operands on an fp32 state (MMPFN_AUTOCAST=bf16)
@@ -136,6 +137,9 @@ SIGNATURES = [
     ("mmpfn_set_full_last_layer", _i, [_vp, _i]),
     ("mmpfn_bar_head", _i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp,
                             _vp, _vp]),
+    ("mmpfn_bar_score", _i, [_vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    ("mmpfn_bar_head_score", _i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp,
+                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
 ]
 
 # include/mmpfn_modality.h (modality encoders: DINOv2 ViT, ELECTRA text tower)

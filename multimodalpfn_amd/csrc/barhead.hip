@@ -1,6 +1,10 @@
 // Bar-distribution head of the regression ensemble (regressor.py:691-706 with utils.py:659-700, then the
 // renormalised criterion's mean / mode / icdf, bar_distribution.py:239-332,588-597): M members' logits over B bars
 // -> one predictive distribution per test row and its point estimates, in one pass over the logits.  Always fp32.
+// Scoring of a finished row (bar_score_row: the negative log density, CDF, probability of improvement and expected
+// improvement at up to kBarScoreMaxTargets targets per row, and the mean of squares; bar_distribution.py:59-97,
+// 487-571,600-675,706-758) runs from the head itself (bar_head_kernel<NV, true>) or over any logits [Q][B]
+// (bar_score_kernel).
 #include "common.h"
 #include "kernels.h"
 
@@ -75,6 +79,116 @@ __device__ __forceinline__ float bar_block_scan(const float (&e)[NV][4], float (
   return ((t0 + t1) + t2) + t3;
 }
 
+// Half-normal pieces of the two end buckets (bar_distribution.py:677-703): EI of a half-normal of scale s over an
+// incumbent at u * s (u <= 0 is minus the position in the tail), 2 s (phi(u) + u Phi(u)).
+__device__ __forceinline__ float bar_halfnormal_ei(float s, float u) {
+  const float phi = expf(-0.5f * (u * u)) * 0.3989422804f;
+  const float Phi = 0.5f * erfcf(-u * 0.7071067812f);
+  return (2.0f * s) * (phi + u * Phi);
+}
+
+// Scores of a finished row: p_s [ldp] holds the row's probabilities (zero beyond B) and c_s their inclusive
+// cumulative sums, as bar_head_kernel's last stage leaves them, both visible to every thread (a barrier lies between
+// their stores and this call).  m_s [ldp] is scratch for the one extra scan the expected improvement needs.
+// Per row O(B): the mean of squares and the scan of p_b * (mid_b - centre) over the interior buckets (the centre is
+// one of the borders, so borders far from zero cost nothing: every term is as small as the borders' span).  Per
+// target O(log B): thread j < J finds the bucket of ys[j] as searchsorted(borders, y) - 1 does (left side, clamped:
+// the first border >= y; equal borders of a zero-width bucket are fine) and reads what it needs at that bucket.
+// The two end buckets carry the half-normal tails in nll / pi / ei and the piecewise-linear form in cdf, as the
+// reference has them.  A NaN target scores nll 0 and cdf / pi / ei NaN.  Every output pointer may be null.
+// Contraction is pinned: both callers must round alike.
+template <int NV>
+__device__ __forceinline__ void bar_score_row(const float* p_s, const float* c_s, float* m_s, float* red,
+                                              const BarScoreArgs& s, int B, int q) {
+#pragma clang fp contract(off)
+  const bool want_ei = s.ei != nullptr && s.J > 0;
+  if (want_ei || s.mean_of_square) {  // block-uniform
+    float g[NV][4], x[NV][4];
+    float sq = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int j0 = bar_index<NV>(i);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int b = j0 + k;
+        const float p = b < B ? p_s[b] : 0.f;
+        g[i][k] = b < B && want_ei ? p * s.ei_mids[b] : 0.f;
+        if (b < B && s.mean_of_square) sq += p * s.mean_squares[b];
+      }
+    }
+    if (want_ei) {
+      bar_block_scan<NV>(g, x, red);
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        const int j0 = bar_index<NV>(i);
+        if (j0 < B)
+          *reinterpret_cast<f32x4*>(m_s + j0) =
+              f32x4{x[i][0] + g[i][0], x[i][1] + g[i][1], x[i][2] + g[i][2], x[i][3] + g[i][3]};
+      }
+    }
+    if (s.mean_of_square) {
+      sq = bar_block_sum(sq, red);
+      if (threadIdx.x == 0) s.mean_of_square[q] = sq;
+    }
+    __syncthreads();  // m_s before the targets read it
+  }
+  const int j = threadIdx.x;
+  if (j >= s.J) return;
+  const float y = s.ys[(int64_t)q * s.J + j];
+  const bool isnan_y = y != y;
+  int lo = 0, hi = B + 1;  // lower bound of y in borders[0 .. B]
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (s.borders[mid] < y) lo = mid + 1;
+    else hi = mid;
+  }
+  const int b = lo - 1 < 0 ? 0 : lo - 1 > B - 1 ? B - 1 : lo - 1;
+  const float L = s.borders[b], R = s.borders[b + 1], w = s.widths[b], p = p_s[b];
+  const float p0 = p_s[0], pl = p_s[B - 1];
+  const float b1 = s.borders[1], bl = s.borders[B - 1];
+  const float nanv = __builtin_nanf("");
+  const int64_t o = (int64_t)q * s.J + j;
+  if (s.nll) {
+    float lp = logf(p) - s.log_widths[b];
+    if (b == 0) {
+      const float t = fmaxf(b1 - y, 1e-8f);
+      lp += s.ends[kEndK0] - (t * t) * s.ends[kEndInv2Var0];
+    }
+    if (b == B - 1) {
+      const float t = fmaxf(y - bl, 1e-8f);
+      lp += s.ends[kEndKL] - (t * t) * s.ends[kEndInv2VarL];
+    }
+    s.nll[o] = isnan_y ? 0.f : -lp;
+  }
+  const float share = fminf(fmaxf((y - L) / w, 0.0f), 1.0f);
+  if (s.cdf) {
+    float cd = (b > 0 ? c_s[b - 1] : 0.f) + p * share;
+    if (y <= s.borders[0]) cd = 0.f;
+    if (y >= s.borders[B]) cd = 1.f;
+    s.cdf[o] = isnan_y ? nanv : fminf(fmaxf(cd, 0.0f), 1.0f);
+  }
+  // the interior buckets (1 .. B - 2) wholly right of the target, and its own bucket when that is an interior one
+  const bool inner = b >= 1 && b <= B - 2;
+  const float pint = b <= B - 2 ? c_s[B - 2] - c_s[b] : 0.f;
+  const float pos0 = fmaxf(b1 - y, 0.f), posl = fmaxf(y - bl, 0.f);  // positions in the two half-normals
+  if (s.pi) {
+    const float f0 = pos0 > 0.f ? erff(pos0 * s.ends[kEndInvS0] * 0.7071067812f) : 0.f;
+    const float fl = posl > 0.f ? erfcf(posl * s.ends[kEndInvSL] * 0.7071067812f) : 1.f;
+    const float v = (p0 * f0 + pl * fl) + (pint + (inner ? p * (1.0f - share) : 0.f));
+    s.pi[o] = isnan_y ? nanv : v;
+  }
+  if (s.ei) {
+    const float gint = b <= B - 2 ? m_s[B - 1] - m_s[b] : 0.f;
+    const float d = R - y;
+    const float part = inner ? p * ((d * d) / (2.0f * w)) : 0.f;
+    const float s0 = s.ends[kEndS0], sl = s.ends[kEndSL];
+    const float e0 = bar_halfnormal_ei(s0, 0.f) - bar_halfnormal_ei(s0, -pos0 * s.ends[kEndInvS0]);
+    const float el = bar_halfnormal_ei(sl, -posl * s.ends[kEndInvSL]);
+    const float v = (p0 * e0 + pl * el) + ((gint - (y - s.ends[kEndCentre]) * pint) + part);
+    s.ei[o] = isnan_y ? nanv : v;
+  }
+}
+
 struct BarHeadArgs {
   const float* logits;          // [M][Q][B]
   const unsigned char* cancel;  // [M][ldc] or null
@@ -96,8 +210,9 @@ struct BarHeadArgs {
   int tvec, cvec;    // the strides and bases allow 16-byte table loads / 4-byte mask loads (padded rows)
 };
 
-template <int NV>
-__global__ __launch_bounds__(kBarThreads) void bar_head_kernel(const BarHeadArgs a) {
+// SCORE: the scores of the finished row as well (bar_score_row, one more LDS array); without it `s` is not read.
+template <int NV, bool SCORE>
+__global__ __launch_bounds__(kBarThreads) void bar_head_kernel(const BarHeadArgs a, const BarScoreArgs s) {
   extern __shared__ __attribute__((aligned(16))) float bar_lds[];
   __shared__ float red[4];
   __shared__ int red_i[4];
@@ -333,18 +448,99 @@ __global__ __launch_bounds__(kBarThreads) void bar_head_kernel(const BarHeadArgs
     const float left = a.borders[j], right = a.borders[j + 1];
     a.quantiles[(int64_t)k * a.Q + q] = left + (right - left) * rest / p_s[j];
   }
+  if constexpr (SCORE) bar_score_row<NV>(p_s, c_s, bar_lds + 2 * ldp, red, s, B, q);
+}
+
+// Scores of any logits [Q][B]: temperature, softmax and scan as bar_head_kernel's last stage has them (-inf logits
+// are bars of weight zero), then bar_score_row.
+template <int NV>
+__global__ __launch_bounds__(kBarThreads) void bar_score_kernel(const float* logits, int B, float inv_temp,
+                                                                const BarScoreArgs s) {
+  extern __shared__ __attribute__((aligned(16))) float bar_lds[];
+  __shared__ float red[4];
+  const int q = blockIdx.x;
+  const int ldp = (B + 3) & ~3;
+  float* const p_s = bar_lds;
+  float* const c_s = bar_lds + ldp;
+  const float* row = logits + (int64_t)q * B;
+  const bool vec = (reinterpret_cast<uintptr_t>(row) & 15) == 0;
+  float acc[NV][4], e[NV][4], c[NV][4];
+  float mx = -INFINITY;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int j0 = bar_index<NV>(i);
+    if (vec && j0 + 3 < B) {
+      const f32x4 r = *reinterpret_cast<const f32x4*>(row + j0);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) acc[i][k] = r[k];
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) acc[i][k] = j0 + k < B ? row[j0 + k] : -INFINITY;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      acc[i][k] = acc[i][k] * inv_temp;
+      mx = fmaxf(mx, acc[i][k]);
+    }
+  }
+  mx = bar_block_max(mx, red);
+#pragma unroll
+  for (int i = 0; i < NV; ++i)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) e[i][k] = expf(acc[i][k] - mx);
+  const float inv = 1.0f / bar_block_scan<NV>(e, c, red);
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int j0 = bar_index<NV>(i);
+    float pk[4], ck[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      pk[k] = e[i][k] * inv;
+      ck[k] = (c[i][k] + e[i][k]) * inv;
+    }
+    if (j0 < B) {
+      *reinterpret_cast<f32x4*>(p_s + j0) = f32x4{pk[0], pk[1], pk[2], pk[3]};
+      *reinterpret_cast<f32x4*>(c_s + j0) = f32x4{ck[0], ck[1], ck[2], ck[3]};
+    }
+  }
+  __syncthreads();
+  bar_score_row<NV>(p_s, c_s, bar_lds + 2 * ldp, red, s, B, q);
+}
+
+// Dynamic LDS of a block: 2 arrays of B floats (3 with the scores), 64 KiB (96 KiB) at B = 8192 beside the static words
+template <typename Kernel>
+hipError_t bar_lds_optin(std::atomic<uint64_t>& opted, Kernel fn, size_t lds) {
+  if (lds + 64 <= 64 * 1024) return hipSuccess;
+  return lds_optin(opted, (const void*)fn, lds <= 64 * 1024 ? 64 * 1024 : 96 * 1024);
+}
+
+template <int NV, bool SCORE>
+hipError_t bar_head_launch(const BarHeadArgs& a, const BarScoreArgs& s, hipStream_t st) {
+  const size_t lds = (size_t)(SCORE ? 3 : 2) * ((a.B + 3) & ~3) * sizeof(float);
+  static std::atomic<uint64_t> opted{0};
+  const hipError_t e = bar_lds_optin(opted, bar_head_kernel<NV, SCORE>, lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((bar_head_kernel<NV, SCORE>), dim3(a.Q), dim3(kBarThreads), lds, st, a, s);
+  return hipGetLastError();
 }
 
 template <int NV>
-hipError_t bar_head_launch(const BarHeadArgs& a, hipStream_t st) {
-  const size_t lds = (size_t)2 * ((a.B + 3) & ~3) * sizeof(float);  // 64 KiB at B = 8192, beside the static words
-  if (lds + 64 > 64 * 1024) {
-    static std::atomic<uint64_t> opted{0};
-    const hipError_t e = lds_optin(opted, (const void*)bar_head_kernel<NV>, 64 * 1024);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(bar_head_kernel<NV>, dim3(a.Q), dim3(kBarThreads), lds, st, a);
+hipError_t bar_score_launch(const float* logits, int Q, int B, float inv_temp, const BarScoreArgs& s, hipStream_t st) {
+  const size_t lds = (size_t)3 * ((B + 3) & ~3) * sizeof(float);
+  static std::atomic<uint64_t> opted{0};
+  const hipError_t e = bar_lds_optin(opted, bar_score_kernel<NV>, lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(bar_score_kernel<NV>, dim3(Q), dim3(kBarThreads), lds, st, logits, B, inv_temp, s);
   return hipGetLastError();
+}
+
+// What both scoring entry points refuse; `s.J` is set to 0 where no per-target output is asked for.
+bool bar_score_args_ok(BarScoreArgs& s, int B) {
+  const bool per_target = s.nll || s.cdf || s.pi || s.ei;
+  if (B < 2 || B > kBarHeadMaxBars || s.J < 0 || s.J > kBarScoreMaxTargets || (per_target && !s.ys)) return false;
+  if (!s.borders || !s.widths || !s.log_widths || !s.mean_squares || !s.ei_mids || !s.ends) return false;
+  if (!per_target) s.J = 0;
+  return true;
 }
 
 }  // namespace
@@ -352,7 +548,8 @@ hipError_t bar_head_launch(const BarHeadArgs& a, hipStream_t st) {
 hipError_t launch_bar_head(const float* logits, int M, int Q, int B, const unsigned char* cancel, int ldc,
                            const int* idx, const float* share, int ldt, float inv_temp, int avg_before, const float* borders,
                            const float* means, const float* mode_means, const float* widths, const float* levels,
-                           int K, float* out_logits, float* mean, float* mode, float* quantiles, hipStream_t st) {
+                           int K, float* out_logits, float* mean, float* mode, float* quantiles, hipStream_t st,
+                           const BarScoreArgs* score) {
   if (Q <= 0) return hipSuccess;
   if (M <= 0 || M > kBarHeadMaxMembers || B < 1 || B > kBarHeadMaxBars || K < 0 || K > kBarHeadMaxLevels ||
       ldt < B + 1 || (cancel && ldc < B))
@@ -362,10 +559,31 @@ hipError_t launch_bar_head(const float* logits, int M, int Q, int B, const unsig
   const int cvec = cancel && ldc % 4 == 0 && ldc >= ((B + 3) & ~3) && (reinterpret_cast<uintptr_t>(cancel) & 3) == 0;
   const BarHeadArgs a{logits, cancel,  idx,  share, borders, means, mode_means, widths,   levels,
                       out_logits, mean, mode, quantiles, M,  Q,  B,  K,  inv_temp, avg_before, ldt, ldc, tvec, cvec};
-  if (B <= 1024) return bar_head_launch<1>(a, st);
-  if (B <= 2048) return bar_head_launch<2>(a, st);
-  if (B <= 5120) return bar_head_launch<5>(a, st);
-  return bar_head_launch<8>(a, st);
+  if (!score) {
+    const BarScoreArgs none{};
+    if (B <= 1024) return bar_head_launch<1, false>(a, none, st);
+    if (B <= 2048) return bar_head_launch<2, false>(a, none, st);
+    if (B <= 5120) return bar_head_launch<5, false>(a, none, st);
+    return bar_head_launch<8, false>(a, none, st);
+  }
+  BarScoreArgs s = *score;
+  s.borders = borders;
+  s.widths = widths;
+  if (!bar_score_args_ok(s, B)) return hipErrorInvalidValue;
+  if (B <= 1024) return bar_head_launch<1, true>(a, s, st);
+  if (B <= 2048) return bar_head_launch<2, true>(a, s, st);
+  if (B <= 5120) return bar_head_launch<5, true>(a, s, st);
+  return bar_head_launch<8, true>(a, s, st);
+}
+
+hipError_t launch_bar_score(const float* logits, int Q, int B, float inv_temp, const BarScoreArgs& score, hipStream_t st) {
+  if (Q <= 0) return hipSuccess;
+  BarScoreArgs s = score;
+  if (!bar_score_args_ok(s, B)) return hipErrorInvalidValue;
+  if (B <= 1024) return bar_score_launch<1>(logits, Q, B, inv_temp, s, st);
+  if (B <= 2048) return bar_score_launch<2>(logits, Q, B, inv_temp, s, st);
+  if (B <= 5120) return bar_score_launch<5>(logits, Q, B, inv_temp, s, st);
+  return bar_score_launch<8>(logits, Q, B, inv_temp, s, st);
 }
 
 }  // namespace mmpfn

@@ -1122,6 +1122,59 @@ int mmpfn_bar_head(mmpfn_ctx* ctx, const float* logits, int M, int Q, int B, con
   return MMPFN_OK;
 }
 
+static_assert(MMPFN_BAR_MAX_TARGETS == kBarScoreMaxTargets && MMPFN_BAR_SCORE_ENDS == kBarScoreEnds,
+              "the header's scoring limits are the kernel's");
+
+// what both scoring entry points refuse before a launch; null: fine
+static const char* bar_score_refusal(int B, const float* log_widths, const float* mean_squares, const float* ei_mids,
+                                     const float* ends, const float* ys, int J, const float* nll, const float* cdf,
+                                     const float* pi, const float* ei) {
+  if (!log_widths || !mean_squares || !ei_mids || !ends) return "null score table";
+  if (B < 2 || B > MMPFN_BAR_MAX_BARS) return "B outside 2 .. MMPFN_BAR_MAX_BARS";
+  if (J < 0 || J > MMPFN_BAR_MAX_TARGETS) return "J outside 0 .. MMPFN_BAR_MAX_TARGETS";
+  if (!ys && (nll || cdf || pi || ei)) return "a per-target output without targets";
+  return nullptr;
+}
+
+int mmpfn_bar_score(mmpfn_ctx* ctx, const float* logits, int Q, int B, float inv_temperature, const float* borders,
+                    const float* widths, const float* log_widths, const float* mean_squares, const float* ei_mids,
+                    const float* ends, const float* ys, int J, float* nll, float* cdf, float* pi, float* ei,
+                    float* mean_of_square) {
+  if (!ctx) return MMPFN_ERR_INVALID;
+  if (!logits || !borders || !widths || Q < 0 || !(inv_temperature > 0.f))
+    return fail(ctx, MMPFN_ERR_INVALID, "mmpfn_bar_score: null argument, negative size or temperature <= 0");
+  if (const char* why = bar_score_refusal(B, log_widths, mean_squares, ei_mids, ends, ys, J, nll, cdf, pi, ei))
+    return fail(ctx, MMPFN_ERR_INVALID, std::string("mmpfn_bar_score: ") + why);
+  HIPCHK(hipSetDevice(ctx->device));
+  const BarScoreArgs s{borders, widths, log_widths, mean_squares, ei_mids, ends, ys, nll, cdf, pi, ei, mean_of_square, J};
+  HIPCHK(launch_bar_score(logits, Q, B, inv_temperature, s, ctx->stream));
+  return MMPFN_OK;
+}
+
+int mmpfn_bar_head_score(mmpfn_ctx* ctx, const float* logits, int M, int Q, int B, const unsigned char* cancel, int ldc,
+                         const int* idx, const float* share, int ldt, float inv_temperature, int avg_before,
+                         const float* borders, const float* bucket_means, const float* mode_means, const float* widths,
+                         const float* levels, int K, float* out_logits, float* mean, float* mode, float* quantiles,
+                         const float* log_widths, const float* mean_squares, const float* ei_mids, const float* ends,
+                         const float* ys, int J, float* nll, float* cdf, float* pi, float* ei, float* mean_of_square) {
+  if (!ctx) return MMPFN_ERR_INVALID;
+  if (!logits || !idx || !share || !borders || !bucket_means || !mode_means || !widths || !mean || !mode || Q < 0 ||
+      K < 0 || (K > 0 && (!levels || !quantiles)) || !(inv_temperature > 0.f))
+    return fail(ctx, MMPFN_ERR_INVALID, "mmpfn_bar_head_score: null argument, negative size or temperature <= 0");
+  if (ldt < B + 1 || (cancel && ldc < B))
+    return fail(ctx, MMPFN_ERR_INVALID, "mmpfn_bar_head_score: ldt < B + 1 or ldc < B");
+  if (M < 1 || M > MMPFN_BAR_MAX_MEMBERS || K > MMPFN_BAR_MAX_LEVELS)
+    return fail(ctx, MMPFN_ERR_INVALID, "mmpfn_bar_head_score: M or K beyond the kernel (M " + std::to_string(M) +
+                                            ", K " + std::to_string(K) + ")");
+  if (const char* why = bar_score_refusal(B, log_widths, mean_squares, ei_mids, ends, ys, J, nll, cdf, pi, ei))
+    return fail(ctx, MMPFN_ERR_INVALID, std::string("mmpfn_bar_head_score: ") + why);
+  HIPCHK(hipSetDevice(ctx->device));
+  const BarScoreArgs s{borders, widths, log_widths, mean_squares, ei_mids, ends, ys, nll, cdf, pi, ei, mean_of_square, J};
+  HIPCHK(launch_bar_head(logits, M, Q, B, cancel, ldc, idx, share, ldt, inv_temperature, avg_before, borders, bucket_means,
+                         mode_means, widths, levels, K, out_logits, mean, mode, quantiles, ctx->stream, &s));
+  return MMPFN_OK;
+}
+
 int mmpfn_status(mmpfn_ctx* ctx) {
   if (!ctx) return MMPFN_ERR_INVALID;
   HIPCHK(hipSetDevice(ctx->device));

@@ -266,10 +266,46 @@ hipError_t launch_aggregate(const float* logits /*[M][Q][n_out]*/, int M, int Q,
 // (ldt >= B + 1) are the host's per-border tables (idx -1 / -2: the CDF forced to 0 / 1); cancel [M][ldc] bytes
 // (ldc >= B) or null.  Rows padded to a multiple of 4 entries (and 16-byte bases) are read in 16- / 4-byte pieces.
 constexpr int kBarHeadMaxBars = 8192, kBarHeadMaxMembers = 1024, kBarHeadMaxLevels = 64;
+struct BarScoreArgs;  // below; non-null: the finished row's scores as well
 hipError_t launch_bar_head(const float* logits, int M, int Q, int B, const unsigned char* cancel, int ldc,
                            const int* idx, const float* share, int ldt, float inv_temp, int avg_before, const float* borders,
                            const float* means, const float* mode_means, const float* widths, const float* levels,
-                           int K, float* out_logits, float* mean, float* mode, float* quantiles, hipStream_t st);
+                           int K, float* out_logits, float* mean, float* mode, float* quantiles, hipStream_t st,
+                           const BarScoreArgs* score = nullptr);
+
+// Scores of a finished row of bars (barhead.hip bar_score_row): what depends on the borders alone comes from the host
+// (bar_distribution.FullSupportBarDistribution.score_tables): log_widths / mean_squares / ei_mids [B] and ends
+// [kBarScoreEnds], indexed by the kEnd* below.  ys [Q][J] targets (J <= kBarScoreMaxTargets); nll / cdf / pi / ei
+// [Q][J] and mean_of_square [Q], each may be null.  launch_bar_head takes borders / widths from its own arguments.
+constexpr int kBarScoreMaxTargets = 64, kBarScoreEnds = 9;
+enum BarScoreEnd {
+  kEndS0 = 0,        // scale of the first bucket's half-normal (half its weight inside the bucket's width)
+  kEndSL = 1,        // ... of the last bucket's
+  kEndInvS0 = 2,     // 1 / scale
+  kEndInvSL = 3,
+  kEndInv2Var0 = 4,  // 1 / (2 scale^2)
+  kEndInv2VarL = 5,
+  kEndK0 = 6,        // the half-normal's log density at 0 plus the log of the bucket's width
+  kEndKL = 7,
+  kEndCentre = 8,    // the border ei_mids is centred on
+};
+struct BarScoreArgs {
+  const float* borders;       // [B + 1]
+  const float* widths;        // [B]
+  const float* log_widths;    // [B]
+  const float* mean_squares;  // [B]
+  const float* ei_mids;       // [B] plain bucket means minus ends[kEndCentre]; 0 in the two end buckets
+  const float* ends;          // [kBarScoreEnds]
+  const float* ys;            // [Q][J] or null
+  float* nll;
+  float* cdf;
+  float* pi;
+  float* ei;
+  float* mean_of_square;
+  int J;
+};
+hipError_t launch_bar_score(const float* logits /*[Q][B]*/, int Q, int B, float inv_temp, const BarScoreArgs& score,
+                            hipStream_t st);
 
 // ---- mixer helpers -----------------------------------------------------------------
 hipError_t launch_layernorm_rows(const float* in, int64_t rows, int dim, float eps, void* out, DType out_t,

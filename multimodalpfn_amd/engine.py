@@ -492,15 +492,72 @@ class HipEngine:
         )
         return out
 
+    SCORE_KINDS = ("nll", "cdf", "pi", "ei", "mean_of_square")  # mmpfn_bar_score's outputs; the last one is per row
+
+    def _score_tables(self, tables: dict, B: int, keys) -> dict:
+        tabs = {k: self._dev(tables[k]).reshape(-1) for k in keys}
+        sizes = {"borders": B + 1, "ends": _lib.BAR_SCORE_ENDS}
+        if any(t.numel() != sizes.get(k, B) for k, t in tabs.items()):
+            raise ValueError(f"score tables do not fit {B} bars")
+        return tabs
+
+    def _score_buffers(self, ys, Q: int, B: int, want) -> tuple:
+        """Device targets ``[Q, J]`` (``[Q]`` is one target per row) and one output tensor per wanted kind."""
+        unknown = set(want) - set(self.SCORE_KINDS)
+        if unknown:
+            raise ValueError(f"unknown score kinds {sorted(unknown)}")
+        if not 2 <= B <= _lib.BAR_MAX_BARS:
+            raise ValueError(f"mmpfn_bar_score holds 2..{_lib.BAR_MAX_BARS} bars; got {B}")
+        per_target = [k for k in want if k != "mean_of_square"]
+        yd, J = None, 0
+        if ys is not None:
+            yd = self._dev(ys)
+            yd = (yd[:, None] if yd.dim() == 1 else yd).contiguous()
+            if yd.dim() != 2 or yd.shape[0] != Q:
+                raise ValueError(f"targets [{Q}] or [{Q}, J] expected, got {tuple(yd.shape)}")
+            J = yd.shape[1]
+            if not 1 <= J <= _lib.BAR_MAX_TARGETS:
+                raise ValueError(f"mmpfn_bar_score holds 1..{_lib.BAR_MAX_TARGETS} targets per row; got {J}")
+        elif per_target:
+            raise ValueError(f"{per_target} need targets")
+        out = {k: torch.empty((Q,) if k == "mean_of_square" else (Q, J), device=self.device, dtype=torch.float32)
+               for k in want}
+        return yd, J, out
+
+    def bar_score(self, logits: torch.Tensor, criterion_tables: dict, ys, *, softmax_temperature: float = 1.0,
+                  want=SCORE_KINDS) -> dict:
+        """Scores of the bar distributions ``softmax(logits / softmax_temperature)`` ``[Q, B]`` at the targets ``ys``
+        ``[Q, J]`` (or ``[Q]``; ``None`` when only ``mean_of_square`` is wanted) on the device (``mmpfn_bar_score``).
+        ``criterion_tables``: ``FullSupportBarDistribution.head_tables()`` and ``.score_tables()`` in one dict.
+        Returns device tensors, the kinds in ``want``: ``nll`` / ``cdf`` / ``pi`` / ``ei`` ``[Q, J]`` (the target as
+        ``best_f``), ``mean_of_square`` ``[Q]``."""
+        lg = logits.to(self.device, torch.float32).contiguous()
+        Q, B = lg.shape
+        if not softmax_temperature > 0:
+            raise ValueError(f"softmax_temperature must be > 0, got {softmax_temperature}")
+        yd, J, out = self._score_buffers(ys, Q, B, want)
+        t = self._score_tables(criterion_tables, B, ("borders", "widths", "log_widths", "mean_squares", "ei_mids", "ends"))
+        self._bind_stream()
+        self._check(
+            self.lib.mmpfn_bar_score(self.ctx, _ptr(lg), Q, B, 1.0 / float(softmax_temperature), _ptr(t["borders"]),
+                                     _ptr(t["widths"]), _ptr(t["log_widths"]), _ptr(t["mean_squares"]),
+                                     _ptr(t["ei_mids"]), _ptr(t["ends"]), _ptr(yd), J,
+                                     *(_ptr(out.get(k)) for k in self.SCORE_KINDS)),
+            "mmpfn_bar_score",
+        )
+        return out
+
     def bar_head(self, logits: torch.Tensor, idx, share, criterion: dict, *, cancel=None,
                  softmax_temperature: float = 1.0, average_before_softmax: bool = False, quantiles=(),
-                 want_logits: bool = False) -> dict:
+                 want_logits: bool = False, targets=None, score_tables: dict | None = None) -> dict:
         """Regression post-processing of regressor.py:652-765 on the device (``mmpfn_bar_head``).
 
         ``logits`` ``[M, Q, B]``; ``idx`` / ``share`` ``[M, B + 1]`` from ``bar_distribution.border_tables``;
         ``cancel`` ``[M, B]`` bool or ``None``; ``criterion``: ``FullSupportBarDistribution.head_tables()`` of the
         renormalised criterion.  Returns device tensors ``mean`` / ``mode`` ``[Q]``, ``quantiles`` ``[K, Q]`` and
-        ``logits`` ``[Q, B]`` (``None`` unless ``want_logits``)."""
+        ``logits`` ``[Q, B]`` (``None`` unless ``want_logits``).  With ``targets`` ``[Q, J]`` (or ``[Q]``) and
+        ``score_tables`` (``FullSupportBarDistribution.score_tables()``) the same kernel scores every finished row
+        (``mmpfn_bar_head_score``) and ``bar_score``'s keys come back as well."""
         lg = logits.to(self.device, torch.float32).contiguous()
         M, Q, B = lg.shape
         if B > _lib.BAR_MAX_BARS or M > _lib.BAR_MAX_MEMBERS or len(quantiles) > _lib.BAR_MAX_LEVELS or B < 1 or M < 1:
@@ -528,15 +585,27 @@ class HipEngine:
         mean = torch.empty((Q,), device=self.device, dtype=torch.float32)
         mode = torch.empty((Q,), device=self.device, dtype=torch.float32)
         qs = torch.empty((K, Q), device=self.device, dtype=torch.float32)
+        head_args = (self.ctx, _ptr(lg), M, Q, B, _ptr(cm), ldc, _ptr(ix), _ptr(sh), ldt,
+                     1.0 / float(softmax_temperature), int(average_before_softmax), _ptr(tabs["borders"]),
+                     _ptr(tabs["bucket_means"]), _ptr(tabs["mode_means"]), _ptr(tabs["widths"]), _ptr(lv),
+                     K, _ptr(out), _ptr(mean), _ptr(mode), _ptr(qs) if K else None)
+        res = {"mean": mean, "mode": mode, "quantiles": qs, "logits": out}
+        if targets is None:
+            self._bind_stream()
+            self._check(self.lib.mmpfn_bar_head(*head_args), "mmpfn_bar_head")
+            return res
+        if score_tables is None:
+            raise ValueError("targets need score_tables")
+        yd, J, scores = self._score_buffers(targets, Q, B, self.SCORE_KINDS)
+        st = self._score_tables(score_tables, B, ("log_widths", "mean_squares", "ei_mids", "ends"))
         self._bind_stream()
         self._check(
-            self.lib.mmpfn_bar_head(self.ctx, _ptr(lg), M, Q, B, _ptr(cm), ldc, _ptr(ix), _ptr(sh), ldt,
-                                    1.0 / float(softmax_temperature), int(average_before_softmax), _ptr(tabs["borders"]),
-                                    _ptr(tabs["bucket_means"]), _ptr(tabs["mode_means"]), _ptr(tabs["widths"]), _ptr(lv),
-                                    K, _ptr(out), _ptr(mean), _ptr(mode), _ptr(qs) if K else None),
-            "mmpfn_bar_head",
+            self.lib.mmpfn_bar_head_score(*head_args, _ptr(st["log_widths"]), _ptr(st["mean_squares"]),
+                                          _ptr(st["ei_mids"]), _ptr(st["ends"]), _ptr(yd), J,
+                                          *(_ptr(scores[k]) for k in self.SCORE_KINDS)),
+            "mmpfn_bar_head_score",
         )
-        return {"mean": mean, "mode": mode, "quantiles": qs, "logits": out}
+        return {**res, **scores}
 
     def status(self) -> None:
         """Wait for every stream the context ran on and raise ``ValueError`` if any forward since the

@@ -8,6 +8,8 @@ Every forward runs in ``libmmpfn_hip.so`` on an MI355X, and so does the whole po
 ``regressor.py:652-765`` -- temperature, cancel mask, each member's distribution moved onto the criterion's
 borders, the ensemble mean, and the criterion's mean / median / mode / quantiles -- in one kernel over the
 members' logits where they lie (``mmpfn_bar_head``); only what the ``output_type`` asks for is copied back.
+``score_samples`` (log predictive density) and ``acquisition`` (``ei`` / ``pi`` / ``ucb``) score the rows in that same
+kernel (``mmpfn_bar_head_score``).
 There is no CPU forward: without a ROCm GPU ``fit`` / ``predict`` raise the engine's ``RuntimeError``.
 """
 
@@ -243,9 +245,13 @@ class MMPFNRegressor(RegressorMixin, BaseEstimator):
         return tables
 
     def predict_device(self, X, image_test: np.ndarray | None, *, quantiles: Sequence[float] = (),
-                       want_logits: bool = False) -> dict:
+                       want_logits: bool = False, targets=None) -> dict:
         """The head's outputs left on the GPU: ``mean`` / ``mode`` ``[Q]``, ``quantiles`` ``[K, Q]``, ``logits``
-        ``[Q, B]`` or None, and the members' logits ``member_logits`` ``[M, Q, B]``."""
+        ``[Q, B]`` or None, and the members' logits ``member_logits`` ``[M, Q, B]``.  With ``targets`` ``[Q]`` or
+        ``[Q, J]`` on the target's original scale (the renormalised criterion's borders are on that scale) the same
+        kernel scores every row's distribution there: ``nll`` (the negative log density, 0 at a NaN target), ``cdf``,
+        ``pi`` and ``ei`` (the target as the incumbent) ``[Q, J]``, and ``mean_of_square`` / ``variance`` ``[Q]`` --
+        the ``[Q, B]`` log-probabilities reach memory only with ``want_logits``."""
         check_is_fitted(self)
         if X is not None:
             X = validate_X_predict(X, self)
@@ -260,12 +266,36 @@ class MMPFNRegressor(RegressorMixin, BaseEstimator):
         idx, share, cancel = self._member_tables(configs)
         stacked = torch.stack(logits)
         eng = self.model_.engine(stacked.device)
-        out = eng.bar_head(stacked, idx, share, self.renormalized_criterion_.head_tables(), cancel=cancel,
+        crit = self.renormalized_criterion_
+        out = eng.bar_head(stacked, idx, share, crit.head_tables(), cancel=cancel,
                            softmax_temperature=float(self.softmax_temperature),
                            average_before_softmax=bool(self.average_before_softmax), quantiles=list(quantiles),
-                           want_logits=want_logits)
+                           want_logits=want_logits, targets=targets,
+                           score_tables=None if targets is None else crit.score_tables())
+        if targets is not None:
+            out["variance"] = out["mean_of_square"] - out["mean"].square()
         out["member_logits"] = stacked
         return out
+
+    def score_samples(self, X, image_test: np.ndarray | None, y) -> np.ndarray:
+        """The log predictive density of ``y`` ``[Q]`` (original scale) under each row's distribution, ``[Q]``; 0
+        where ``y`` is NaN.  Scored on the device: no ``[Q, B]`` logits are stored or copied."""
+        y = np.asarray(y, dtype=np.float32).reshape(-1)
+        nll = self.predict_device(X, image_test, targets=y)["nll"][:, 0]
+        return (0.0 - nll).cpu().numpy()
+
+    def acquisition(self, X, image_test: np.ndarray | None, best_f, *, kind: Literal["ei", "pi", "ucb"] = "ei",
+                    rest_prob: float = (1 - 0.682) / 2) -> np.ndarray:
+        """A Bayesian-optimisation acquisition value per row, ``[Q]`` (maximising): the expected improvement over /
+        the probability of improving on the incumbent ``best_f`` (a number or one per row, original scale), or
+        ``ucb``, the quantile that leaves ``rest_prob`` above it (``best_f`` unused, as in the reference)."""
+        if kind not in ("ei", "pi", "ucb"):
+            raise ValueError(f"Invalid acquisition kind: {kind}")
+        if kind == "ucb":
+            return self.predict_device(X, image_test, quantiles=[1.0 - rest_prob])["quantiles"][0].cpu().numpy()
+        n_rows = len(X) if X is not None else len(image_test)
+        best = np.array(np.broadcast_to(np.asarray(best_f, dtype=np.float32), (n_rows,)))
+        return self.predict_device(X, image_test, targets=best)[kind][:, 0].cpu().numpy()
 
     def predict(self, X, image_test: np.ndarray | None, *,
                 output_type: Literal["mean", "median", "mode", "quantiles", "full", "main"] = "mean",

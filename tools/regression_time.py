@@ -1,6 +1,7 @@
 """Timing of the regression path's two new pieces at the reference's sizes (8 members, Q = 460 test rows, 5000 bars):
 
-* the bar-distribution head (``mmpfn_bar_head``), with and without the ``[Q, B]`` logits output;
+* the bar-distribution head (``mmpfn_bar_head``), with and without the ``[Q, B]`` logits output, and with every row
+  scored at 1 and at 64 targets in the same kernel (``mmpfn_bar_head_score``);
 * the same head as the restatement's torch operations on the device (the only "before" there is);
 * the wide decoder per member (``mmpfn_decode`` on a value-target model) in the fp32, bf16 and fp16 modes.
 
@@ -18,7 +19,7 @@ sys.path[:0] = [str(ROOT), str(ROOT / "tests"), str(ROOT / "tests" / "golden")]
 
 import regression_oracle as ro  # noqa: E402
 
-from multimodalpfn_amd.bar_distribution import border_tables  # noqa: E402
+from multimodalpfn_amd.bar_distribution import FullSupportBarDistribution, border_tables  # noqa: E402
 from multimodalpfn_amd.engine import HipEngine  # noqa: E402
 from multimodalpfn_amd.model.spec import ModelConfig  # noqa: E402
 
@@ -112,6 +113,26 @@ def main():
         say(f"  bar_head_kernel alone (tables resident), logits output {'on ' if want else 'off'}: "
             f"{min(t) * 1e3:.1f} us (windows {', '.join(f'{v * 1e3:.1f}' for v in t)}); "
             f"{logits.numel() * 4 / (min(t) * 1e-3) / 1e12:.2f} TB/s of member logits")
+    # the head with every row scored in the same kernel (mmpfn_bar_head_score), J targets per row, no logits output
+    d_score = {k: v.to(dev) for k, v in FullSupportBarDistribution(crit["borders"]).score_tables().items()}
+    lo, hi = float(crit["borders"][0]), float(crit["borders"][-1])
+    for J in (1, 64):
+        ys = (lo + (hi - lo) * torch.rand(Q, J, generator=g)).to(dev)
+        outs = [torch.empty(Q, J, device=dev) for _ in range(4)] + [torch.empty(Q, device=dev)]
+
+        def call_scored():
+            rc = eng.lib.mmpfn_bar_head_score(eng.ctx, logits.data_ptr(), M, Q, B, d_cancel.data_ptr(), ldc,
+                                              d_idx.data_ptr(), d_share.data_ptr(), ldt, 1 / 0.9, 0,
+                                              d_crit["borders"].data_ptr(), d_crit["bucket_means"].data_ptr(),
+                                              d_crit["mode_means"].data_ptr(), d_crit["widths"].data_ptr(),
+                                              d_lv.data_ptr(), len(LEVELS), None, o_mean.data_ptr(), o_mode.data_ptr(),
+                                              o_q.data_ptr(), d_score["log_widths"].data_ptr(),
+                                              d_score["mean_squares"].data_ptr(), d_score["ei_mids"].data_ptr(),
+                                              d_score["ends"].data_ptr(), ys.data_ptr(), J, *(o.data_ptr() for o in outs))
+            assert rc == 0
+        t = timed(call_scored, 200)
+        say(f"  bar_head_kernel with the scores (tables resident), J = {J:2d} targets per row: "
+            f"{min(t) * 1e3:.1f} us (windows {', '.join(f'{v * 1e3:.1f}' for v in t)})")
     frm_d = [torch.from_numpy(f).to(dev) for f, _ in sets]
     to_d = torch.from_numpy(std).to(dev)
     masks_d = torch.from_numpy(cancel).to(dev)
