@@ -133,7 +133,6 @@ SIGNATURES = [
     ("mmpfn_kernel_timing_read", _i, [_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64),
                                       ctypes.POINTER(ctypes.c_double)]),
     ("mmpfn_siphash24_rows", _i, [_vp, _i64, _i64, _vp]),
-    ("mmpfn_set_parity_attention_min_keys", _i, [_i, _i]),
     ("mmpfn_set_full_last_layer", _i, [_vp, _i]),
     ("mmpfn_bar_head", _i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp,
                             _vp, _vp]),

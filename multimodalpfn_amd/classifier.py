@@ -17,7 +17,6 @@ from collections.abc import Sequence
 from pathlib import Path
 from typing import Any, Literal
 
-import os
 
 import numpy as np
 import torch
@@ -284,17 +283,14 @@ class MMPFNClassifier(ClassifierMixin, BaseEstimator):
         """Class probabilities ``[Q, n_classes]`` fp32 left on the GPU (no rounding)."""
         check_is_fitted(self)
         ex = self.executor_
-        # the NaN / error check after the aggregation is enqueued (MMPFN_DEFER_STATUS=0: before it; A/B switch)
-        defer = hasattr(ex, "check_status") and os.environ.get("MMPFN_DEFER_STATUS", "1") != "0"
         try:
-            if image_test is not None and hasattr(ex, "launch_mixer_early"):
+            if image_test is not None:
                 # the mixer first: it does not need X, so the host's validation / encoding of X runs under it
                 ex.launch_mixer_early(image_test, device=self.device_, autocast=self.use_autocast_)
             if X is not None:
                 X = self._encode_predict_X(X)
             logits, perms = [], []
-            if defer:
-                ex._defer_status = True
+            ex._defer_status = True  # the NaN / error check runs after the aggregation is enqueued (below)
             try:
                 for out, config in ex.iter_outputs(X, image_test=image_test, device=self.device_,
                                                    autocast=self.use_autocast_):
@@ -302,8 +298,7 @@ class MMPFNClassifier(ClassifierMixin, BaseEstimator):
                     logits.append(out)
                     perms.append(config.class_permutation)
             finally:
-                if defer:
-                    ex._defer_status = False
+                ex._defer_status = False
             if any(p is None for p in perms) and not all(p is None for p in perms):
                 raise ValueError("members must either all or none carry a class permutation")
             perm_arr = None if perms[0] is None else np.stack([np.asarray(p) for p in perms])
@@ -317,10 +312,8 @@ class MMPFNClassifier(ClassifierMixin, BaseEstimator):
             # whatever raised (X validation, the member loop, the aggregation): no early mixer tokens stay
             # referenced, and the deferred NaN / HIP check of a member loop that ran still runs (a NaN input's
             # ValueError takes precedence over the error in flight, as before)
-            if hasattr(ex, "_early_tokens"):
-                ex._early_tokens = None
-            if defer:
-                ex.check_status()
+            ex._early_tokens = None
+            ex.check_status()
 
     def predict_proba(self, X, image_test: np.ndarray | None) -> np.ndarray:
         """``classifier.py:517-576``: ensemble-averaged class probabilities ``[Q, n_classes]``."""

@@ -96,11 +96,8 @@ template <int F8> struct P8;
 // e4m3's ETOP balances the two re-run causes on random q / k (round 6; a CPU model of the kernel's per-query scale
 // over N = 1838 / 10 000): 0 sent 94-100 % of the waves back through the underflow guard, 4 sent 25-100 %
 // through overflow of the later tiles' maxima; 2 re-runs 16-19 %
-#ifndef P8_E4_ETOP
-#define P8_E4_ETOP 2
-#endif
 template <> struct P8<1> {  // e4m3 (max 448 = 2^8.8): >= 6.8 octaves of headroom, 11 below the first max
-  static constexpr int FMT = 0, ETOP = P8_E4_ETOP, EMIN = -9, EMAX = 8;
+  static constexpr int FMT = 0, ETOP = 2, EMIN = -9, EMAX = 8;
   static constexpr float UFLOW = 0x1p-3f;
   static __device__ __forceinline__ s16x2 cvt(s16x2 old, float a, float b, float sc, bool hi) {
     return hi ? __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(old, a, b, sc, true)
@@ -120,10 +117,6 @@ template <> struct P8<2> {  // e5m2 (max 57344 = 2^15.8): >= 8.8 octaves of head
 constexpr int SG_VALU = 0x2, SG_MFMA = 0x8, SG_VMEM_READ = 0x20, SG_DS_READ = 0x100, SG_DS_WRITE = 0x200,
               SG_TRANS = 0x400;
 
-// K / V^T staging of the bf16-V^T kernels by LDS-DMA (no staging registers, no ds_write), 0: register staging
-#ifndef P4_DMA
-#define P4_DMA 1
-#endif
 template <int F8, bool QF16, bool OF16>
 __global__ __launch_bounds__(256, 2) void attn_pipe_kernel(const Attn2Args p) {
   typedef typename Op16<QF16>::t QT;    // Q and K elements
@@ -132,7 +125,8 @@ __global__ __launch_bounds__(256, 2) void attn_pipe_kernel(const Attn2Args p) {
   typedef typename Op16<OF16>::x4 O4;
   // LDS slot: K [64][32] bf16 in 80-B rows | V^T [32][64] in 144-B rows (bf16) or 80-B rows (e4m3);
   // DMA (bf16 V^T): K in 64-B rows | V^T in 128-B rows, unpadded and XOR-swizzled (see the fragments below)
-  constexpr bool DMA = F8 == 0 && P4_DMA;
+  // DMA: K / V^T staging of the bf16-V^T kernels by LDS-DMA (no staging registers, no ds_write); F8: register staging
+  constexpr bool DMA = F8 == 0;
   constexpr int KROW = DMA ? 64 : 80;
   constexpr int VROW = F8 ? 80 : (DMA ? 128 : 144);
   constexpr int P4_SLOT_BYTES = 64 * KROW + 32 * VROW;
@@ -279,14 +273,9 @@ __global__ __launch_bounds__(256, 2) void attn_pipe_kernel(const Attn2Args p) {
     lds_dma16(vdo, Vg + t * P4_KT,
              __builtin_amdgcn_readfirstlane(lds0 + slot * P4_SLOT_BYTES + VBASE + wave * 1024));
   };
-  // staging registers: P4_LEAD = 1: one set, tile t+3 loaded in step t and written to LDS in step t+1;
-  // P4_LEAD = 2: two sets (tile j in set j & 1), tile t+4 loaded in step t, written in step t+2, so a load has
-  // two steps to land instead of one (ablation: the K / V^T global loads cost ~40 us of a 258 us launch)
-#ifndef P4_LEAD
-#define P4_LEAD 2
-#endif
-  constexpr int LEAD = P4_LEAD;
-  static_assert(LEAD == 1 || LEAD == 2, "staging lead");
+  // staging registers: two sets (tile j in set j & 1), tile t+4 loaded in step t, written in step t+2, so a load has
+  // two steps to land (ablation: the K / V^T global loads cost ~40 us of a 258 us launch)
+  constexpr int LEAD = 2;
   u32x4 rk[LEAD];
   VStage rv[LEAD];
   auto gload = [&](int t, u32x4& k, VStage& v) __attribute__((always_inline)) {
@@ -439,29 +428,9 @@ __global__ __launch_bounds__(256, 2) void attn_pipe_kernel(const Attn2Args p) {
   // the order of one pipeline step: 12 MFMAs (S0-S3 32x32, then P.V 32x32 / row-sum 16x16 pairs), 32
   // exps, 16 conversions and the step's LDS / global traffic.  An MFMA holds vector issue for 8 cycles;
   // a filler is free while the gap's issue sum fits the MFMA (32 / 16 cycles) and costs extra once it
-  // overflows (MI355X_MICROARCH.md constants), so each gap carries exactly its budget (P4_PIN 1: three
-  // exps per 32x32, one per 16x16) and the conversions + remaining exps follow in an MFMA-free tail
-#ifndef P4_PIN
-#define P4_PIN 1
-#endif
+  // overflows (MI355X_MICROARCH.md constants), so each gap carries exactly its budget (three exps per 32x32,
+  // one per 16x16) and the conversions + remaining exps follow in an MFMA-free tail
   auto pin_step = [&](bool mem) __attribute__((always_inline)) {
-#if P4_PIN == 0
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
-      if (mem) __builtin_amdgcn_sched_group_barrier(SG_DS_READ, 2, 0);
-      __builtin_amdgcn_sched_group_barrier(SG_TRANS, 3, 0);
-      __builtin_amdgcn_sched_group_barrier(SG_VALU, 1, 0);
-      if (mem && i == 1) __builtin_amdgcn_sched_group_barrier(SG_DS_WRITE, 2, 0);
-      if (mem && i == 2) __builtin_amdgcn_sched_group_barrier(SG_VMEM_READ, 2, 0);
-      __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(SG_TRANS, 3, 0);
-      __builtin_amdgcn_sched_group_barrier(SG_VALU, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(SG_TRANS, 2, 0);
-      __builtin_amdgcn_sched_group_barrier(SG_VALU, 2, 0);
-    }
-#else
     if constexpr (F8 != 0) {
       // S MFMAs (32 cycles): 3 exps each; P.V 32x32x64 (64 cycles): 7; row sum 16x16x128 (32 cycles): 3
 #pragma unroll
@@ -495,16 +464,11 @@ __global__ __launch_bounds__(256, 2) void attn_pipe_kernel(const Attn2Args p) {
       __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
       __builtin_amdgcn_sched_group_barrier(SG_TRANS, 3, 0);
       __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(SG_TRANS, P4_PIN == 2 ? 0 : 1, 0);
+      __builtin_amdgcn_sched_group_barrier(SG_TRANS, 1, 0);
     }
-    // tail: the remaining exps and the 16 conversions, then the staging traffic
-    __builtin_amdgcn_sched_group_barrier(SG_TRANS, P4_PIN == 2 ? 8 : 4, 0);
+    // tail: the remaining exps and the 16 conversions (the bf16-V^T kernels stage by DMA: no staging traffic to place)
+    __builtin_amdgcn_sched_group_barrier(SG_TRANS, 4, 0);
     __builtin_amdgcn_sched_group_barrier(SG_VALU, 16, 0);
-    if (mem && !DMA) {
-      __builtin_amdgcn_sched_group_barrier(SG_DS_WRITE, 2, 0);
-      __builtin_amdgcn_sched_group_barrier(SG_VMEM_READ, 2, 0);
-    }
-#endif
   };
 
   // ---- fast pass: fixed reference 0 over the full tiles, pipelined by (tile, chain) units
@@ -529,7 +493,7 @@ __global__ __launch_bounds__(256, 2) void attn_pipe_kernel(const Attn2Args p) {
     }
     if constexpr (!DMA) {
       gload(tile_of(min(2, ntiles - 1)), rk[0], rv[0]);
-      if constexpr (LEAD == 2) gload(tile_of(min(3, ntiles - 1)), rk[1], rv[1]);
+      gload(tile_of(min(3, ntiles - 1)), rk[1], rv[1]);
     }
     lds_barrier();
     AP_STAMP(2);
@@ -549,9 +513,9 @@ __global__ __launch_bounds__(256, 2) void attn_pipe_kernel(const Attn2Args p) {
         lstore(ring + ((t + 2) & 3) * P4_SLOT_BYTES, rk[0], rv[0]);
         gload(tile_of(min(t + 2 + LEAD, ntiles - 1)), rk[0], rv[0]);
         lds_barrier();
-        if (LEAD == 2 && t + 1 < ntiles) {
-          lstore(ring + ((t + 3) & 3) * P4_SLOT_BYTES, rk[LEAD - 1], rv[LEAD - 1]);
-          gload(tile_of(min(t + 5, ntiles - 1)), rk[LEAD - 1], rv[LEAD - 1]);
+        if (t + 1 < ntiles) {
+          lstore(ring + ((t + 3) & 3) * P4_SLOT_BYTES, rk[1], rv[1]);
+          gload(tile_of(min(t + 5, ntiles - 1)), rk[1], rv[1]);
           lds_barrier();
         }
       }
@@ -607,7 +571,7 @@ __global__ __launch_bounds__(256, 2) void attn_pipe_kernel(const Attn2Args p) {
       constexpr int S0 = L * P4_SLOT_BYTES, S1 = ((L + 1) & 3) * P4_SLOT_BYTES, S2 = ((L + 2) & 3) * P4_SLOT_BYTES;
       readk(kf[B], ring + S1);
       readv(vf[B], ring + S0);
-      constexpr int RS = LEAD == 2 ? A : 0;  // staging set of tile t+2 (and of t+2+LEAD, loaded next)
+      constexpr int RS = A;  // staging set of tile t+2 (and of t+2+LEAD, loaded next)
       if constexpr (!DMA) {
         lstore(ring + S2, rk[RS], rv[RS]);
         gload(tile_of(min(t + 2 + LEAD, ntiles - 1)), rk[RS], rv[RS]);

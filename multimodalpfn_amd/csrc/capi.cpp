@@ -309,10 +309,6 @@ GemmArgs gargs() {
   return a;
 }
 
-#ifndef MMPFN_F16_QK_BF16
-#define MMPFN_F16_QK_BF16 1  // PREC_F16's item Q / K in bf16 (0: fp16, S on the f16 MFMA; a diagnostics variant)
-#endif
-
 // a public precision code, decoded once (decode_prec) for the forward or the tap that it selects
 struct PrecMode {
   int base = PREC_F32;  // the mode the layer kernels run: PREC_F32, PREC_F32_MFMA, PREC_BF16 or PREC_F16
@@ -328,7 +324,6 @@ struct PrecMode {
   int state_bytes() const { return f16() ? 2 : 4; }
   int op_bytes() const { return is16() ? 2 : 4; }  // Q / K / V^T and the 16-bit modes' GEMM operands
   // the 16-bit modes' item attention: bf16 Q, K and V^T (every MFMA a bf16 one); O in the state's 16-bit type
-  DType qk() const { return f16() && !MMPFN_F16_QK_BF16 ? DType::F16 : DType::BF16; }
   DType attn_out() const { return f16() ? DType::F16 : DType::BF16; }
 };
 // T: tokens per table row (T < 0: a row-wise sublayer, no token limit).  PREC_F16's layer kernels hold a row's tokens
@@ -358,7 +353,7 @@ int project_qkv(mmpfn_ctx* ctx, PrecMode pm, bool rows16, const void* X, const Q
   for (int i = 0; i < nset; ++i) rs[i] = sets[i].r;
   if (pm.is16() && rows16) {
     for (int i = 0; i < nset; ++i) rs[i].W = sets[i].w.op16(pm.w16());
-    HIPCHK(launch_rowgemm_qkv(X, rs, nset, Q, K, Vt, S, Npad, H, st, pm.state(), pm.qk()));
+    HIPCHK(launch_rowgemm_qkv(X, rs, nset, Q, K, Vt, S, Npad, H, st, pm.state()));
   } else if (pm.base == PREC_F32) {  // parity mode: split-bf16 products, every set in one launch (rowgemm3.hip)
     for (int i = 0; i < nset; ++i) rs[i].W = sets[i].w.split.p, rs[i].w_lo = sets[i].w.numel;
     HIPCHK(launch_proj3_qkv((const float*)X, rs, nset, Q, K, Vt, S, Npad, H, st));
@@ -574,7 +569,7 @@ int item_sublayer(mmpfn_ctx* ctx, int l, void* Xv, int S, int T, int N, int Npad
     AttnLayerArgs a{Qi, Kc, Kc + kvl, O, S, TM, H, cc->Npad, cc->N};
     a.a0 = 0, a.na = 0, a.b0 = 0, a.nb = S, a.kvb = 0;  // every row against head 0 of the cache
     a.kv_bstride = (int64_t)cc->Npad * 32;
-    a.q_prescaled = pm.is16(), a.qk_t = pm.qk(), a.o_t = pm.attn_out();
+    a.q_prescaled = pm.is16(), a.o_t = pm.attn_out();  // (qk_t: bf16 in every forward)
     HIPCHK(launch_attn_layer(a, pm.base, st));
   } else {
     if (ctx->cache_out) {  // keep head 0's K / V^T of every column (the test rows' KV, layer.py:344-358)
@@ -589,7 +584,7 @@ int item_sublayer(mmpfn_ctx* ctx, int l, void* Xv, int S, int T, int N, int Npad
     AttnLayerArgs a{Qi, Ki, Vi, O, S, TM, H, Npad, N};
     a.a0 = 0, a.na = N, a.b0 = N, a.nb = Q, a.kvb = 0;
     if (last) a.na = N % ATTN_ITEM_QPB, a.a0 = N - a.na;
-    a.q_prescaled = pm.is16(), a.qk_t = pm.qk(), a.o_t = pm.attn_out();
+    a.q_prescaled = pm.is16(), a.o_t = pm.attn_out();  // (qk_t: bf16 in every forward)
     hipEvent_t* ev = nullptr;
     if (pm.is16()) {  // the live timing and the fp8 P.V exist for the pipelined kernel only
       if (ctx->kt_on && !last) {  // (the roofline's launches all have the full layer's shape)
@@ -1296,8 +1291,6 @@ void mmpfn_cache_free(mmpfn_ctx* ctx, mmpfn_cache* cache) {
   }
   delete cache;
 }
-
-int mmpfn_set_parity_attention_min_keys(int n, int form) { return mmpfn::set_x3_cheap_min_keys(n, form); }
 
 int mmpfn_set_full_last_layer(mmpfn_ctx* ctx, int on) {
   if (!ctx) return MMPFN_ERR_INVALID;

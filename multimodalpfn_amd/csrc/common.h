@@ -145,52 +145,16 @@ __device__ __forceinline__ float gelu_tanh_fast(float x) {
   return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(u));
 }
 
-// the same tanh form on a pair of fp16 values in packed 16-bit arithmetic (fp16 mode, whose hidden
+// the same tanh form on two pairs of fp16 values in packed 16-bit arithmetic (fp16 mode, whose hidden
 // activations are fp16 MFMA operands anyway): v_pk_mul / v_pk_fma / v_pk_add_f16 take one issue slot per
-// pair where the fp32 form takes one per element; v_exp_f16 / v_rcp_f16 per element.  2^u overflowing fp16
-// (x < -5.6) gives rcp(inf) = 0, x * 0 = 0, and underflow gives x: GELU's own limits.
+// pair where the fp32 form takes one per element; v_exp_f16 / v_rcp_f16 per element, the SDWA form writing the
+// high half in place (dst_sel WORD_1, preserve; the compiler's own code spends a v_pack_b32_f16 per pair on it).
+// 2^u overflowing fp16 (x < -5.6) gives rcp(inf) = 0, x * 0 = 0, and underflow gives x: GELU's own limits.
+// From the four fp32 values (h0, h1) (h2, h3) themselves, conversion and the cubic included: the whole two-pair
+// chain in one block, the pairs alternating so that every dependent instruction is one slot behind its producer
+// (the wait state the compiler keeps after v_pk_fma_f16 and after a transcendental), so that no s_nop is needed
+// inside and the block's inputs are old accumulators (no conservative s_nop in front of it either)
 typedef __attribute__((ext_vector_type(2))) _Float16 f16x2_t;
-__device__ __forceinline__ f16x2_t gelu_tanh_h2(f16x2_t x) {
-  constexpr float k = -2.0f * 0.7978845608028654f * 1.4426950408889634f;
-  const f16x2_t kk = {(_Float16)k, (_Float16)k}, kc = {(_Float16)(k * 0.044715f), (_Float16)(k * 0.044715f)};
-  const f16x2_t one = {(_Float16)1.0f, (_Float16)1.0f};
-  const f16x2_t u = x * __builtin_elementwise_fma(kc, x * x, kk);
-  const f16x2_t d = f16x2_t{(_Float16)__builtin_exp2f16(u[0]), (_Float16)__builtin_exp2f16(u[1])} + one;
-  return x * f16x2_t{(_Float16)__builtin_amdgcn_rcph(d[0]), (_Float16)__builtin_amdgcn_rcph(d[1])};
-}
-
-// gelu_tanh_h2 on two pairs at once, bitwise the same values.  The compiler builds each pair's exp / rcp from
-// one v_exp_f16 / v_rcp_f16 on the low half, one SDWA form reading the high half, and a v_pack_b32_f16 (2 of
-// the pair's 12 issue slots); here the SDWA form writes the high half in place (dst_sel WORD_1, preserve).
-// The two pairs alternate so that every read of a transcendental's result comes one instruction after it
-// (gfx950's one-wait-state trans-use rule, which the compiler keeps with s_nop outside asm), and the block
-// ends with non-transcendental instructions.
-__device__ __forceinline__ void gelu_tanh_h2x2(f16x2_t& a, f16x2_t& b) {
-  constexpr float k = -2.0f * 0.7978845608028654f * 1.4426950408889634f;
-  const f16x2_t kk = {(_Float16)k, (_Float16)k}, kc = {(_Float16)(k * 0.044715f), (_Float16)(k * 0.044715f)};
-  const f16x2_t ua = a * __builtin_elementwise_fma(kc, a * a, kk), ub = b * __builtin_elementwise_fma(kc, b * b, kk);
-  f16x2_t ea, eb, ra, rb;
-  asm("v_exp_f16_e32 %0, %4\n\t"
-      "v_exp_f16_e32 %1, %5\n\t"
-      "v_exp_f16_sdwa %0, %4 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1\n\t"
-      "v_exp_f16_sdwa %1, %5 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1\n\t"
-      "v_pk_add_f16 %0, %0, 1.0 op_sel_hi:[1,0]\n\t"
-      "v_pk_add_f16 %1, %1, 1.0 op_sel_hi:[1,0]\n\t"
-      "v_rcp_f16_e32 %2, %0\n\t"
-      "v_rcp_f16_e32 %3, %1\n\t"
-      "v_rcp_f16_sdwa %2, %0 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1\n\t"
-      "v_rcp_f16_sdwa %3, %1 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1\n\t"
-      "v_pk_mul_f16 %2, %6, %2\n\t"
-      "v_pk_mul_f16 %3, %7, %3"
-      : "=&v"(ea), "=&v"(eb), "=&v"(ra), "=&v"(rb)
-      : "v"(ua), "v"(ub), "v"(a), "v"(b));
-  a = ra, b = rb;
-}
-
-// gelu_tanh_h2x2 from the four fp32 values (h0, h1) (h2, h3) themselves, conversion and the cubic included: the
-// whole two-pair chain in one block, every dependent instruction one slot behind its producer (the wait state
-// the compiler keeps after v_pk_fma_f16 and after a transcendental), so that no s_nop is needed inside and the
-// block's inputs are old accumulators (no conservative s_nop in front of it either)
 __device__ __forceinline__ void gelu_tanh_h2x2_f32(float h0, float h1, float h2, float h3, f16x2_t& a, f16x2_t& b) {
   constexpr float k = -2.0f * 0.7978845608028654f * 1.4426950408889634f;
   const f16x2_t kk = {(_Float16)k, (_Float16)k}, kc = {(_Float16)(k * 0.044715f), (_Float16)(k * 0.044715f)};

@@ -143,10 +143,7 @@ __global__ __launch_bounds__(256, NT <= 3 ? 2 : 1) void feat_rows_kernel(void* _
   // all at the barrier (an LDS-DMA's issue cost grows with the other issues of its phase, MI355X_MICROARCH.md; the
   // fp16 form: 102.8 against 106.7 us when measured, profiles/r04/ab_feat_rows_dma_spread.txt; the bf16 form, not
   // measured with it, issues at the barrier)
-#ifndef FR_DMA_SPREAD
-#define FR_DMA_SPREAD 1
-#endif
-  constexpr bool SPREAD = FR_DMA_SPREAD && F16;
+  constexpr bool SPREAD = F16;
   auto dma_start = [&](int item) {  // at the barrier: the whole item, or its tail with the parts to follow
     if constexpr (SPREAD) dma_tail(item);
     else dma_grp(item);

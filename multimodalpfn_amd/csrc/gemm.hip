@@ -395,10 +395,7 @@ hipError_t launch_t(const GemmArgs& a, int groups, hipStream_t st) {
 // wave are the a / b halves of the same 16 output columns.
 constexpr int GB_M = 256, GB_N = 256;
 static_assert(GB_M + GB_N == RING_ROWS, "one ring stage");
-#ifndef GB_STAGES
-#define GB_STAGES 4
-#endif
-constexpr int GB_NST = GB_STAGES;                   // ring stages (128 KB)
+constexpr int GB_NST = 4;                           // ring stages (128 KB)
 constexpr int GB_OST = GB_N / 2 + 8;                // output staging row stride (bf16)
 constexpr int GB_MT = GB_M / 32;                    // 16-row MFMA tiles per wave (8)
 

@@ -124,10 +124,10 @@ struct RowSet {
 //   QKV: one or two row sets of X (train rows: q|k|v, test rows: q; W [N][192]) in ONE launch, the second set's blocks
 //        last; one set launches that set's blocks alone
 //   RES_LN: X <- LN(X + O . W^T), O [M][192] bf16, W [192][192] bf16
-//   x_t: the state's type, fp32 (bf16 W, Q / K; qk_t bf16) or fp16 (PREC_F16: X fp16, W fp16, Q / K in qk_t, fp16
-//   or bf16; V^T stays bf16); RES_LN: O bf16 / X fp32, or both fp16 with W rows in f16_row_perm order (weight_pack.h)
+//   x_t: the state's type, fp32 (bf16 W) or fp16 (PREC_F16: X fp16, W fp16); Q / K and V^T are bf16 in both;
+//   RES_LN: O bf16 / X fp32, or both fp16 with W rows in f16_row_perm order (weight_pack.h)
 hipError_t launch_rowgemm_qkv(const void* X, const RowSet* sets, int nset, void* q, void* k, void* vt, int S, int Npad,
-                              int H, hipStream_t st, DType x_t = DType::F32, DType qk_t = DType::BF16);
+                              int H, hipStream_t st, DType x_t = DType::F32);
 // C = (ln ? LayerNorm(A) : A) . W^T + bias: A fp32, bf16 or fp16 (a_t) [M][192], W [N][192] bf16, C bf16 [M][N], N % 64 == 0;
 // with CT: outputs [vt_from, N) transposed per group of Mk rows into CT [M / Mk][N - vt_from][Mk] (Mk % 32 == 0),
 // C then [M][vt_from]
@@ -187,8 +187,7 @@ hipError_t launch_attn(const AttnArgs& a, int batches, int prec, int waves_per_b
 //     e4m3 (1) or e5m2 (2); vt (bf16) still serves the exact re-run path
 //     qk_t: Q and K bf16, or fp16 (S on the f16 MFMA; then o_t is fp16 too: the fp16 tap); o_t: O bf16 or fp16
 //     (PREC_F16's forward: bf16 Q / K, fp16 O); V^T stays bf16
-//   PREC_F32             attn_item3_kernel on fp32 Q / K / V^T (split bf16 three-product MFMAs), fp32 O, one launch;
-//     its cheap forms by set_x3_cheap_min_keys
+//   PREC_F32             attn_item3_kernel on fp32 Q / K / V^T (split bf16 three-product MFMAs), fp32 O, one launch
 //   PREC_F32_MFMA        attn_item_kernel<0, 4> on fp32 operands: the own-head rows in one launch, the shared-KV rows
 //     in a second (a set of no rows: no launch)
 //   the prescale, fp8 and element-type fields apply to the 16-bit modes only
@@ -210,7 +209,6 @@ constexpr int ATTN_ITEM_QPB = 256;  // queries per task of the 16-bit and PREC_F
 hipError_t launch_attn_layer(const AttnLayerArgs& a, int base_prec, hipStream_t st);
 // bf16 -> e4m3 (saturating) of n elements (n % 8 == 0): the F8 attention's V^T operand
 hipError_t launch_vt_fp8(const void* vt, void* vt8, int64_t n, hipStream_t st);
-int set_x3_cheap_min_keys(int n, int form);  // previous value; mmpfn_set_parity_attention_min_keys
 
 // ---- encoders / decoder ------------------------------------------------------------
 struct SlotParams {  // per (group, slot): how to transform raw column -> model input

@@ -43,11 +43,10 @@ constexpr int LDS_B = 2 * NSLOT * SLOT_B;  // 72 KB per block: two blocks per CU
 constexpr int MP = SLOT_B / 1024 / 4;      // 1-KB DMA pieces per wave, matrix and chunk (3)
 typedef __attribute__((ext_vector_type(2))) float float2_t;
 
-// TT = 16-row tiles per wave: 2 (32 rows, two waves per SIMD, accumulators in VGPRs) or 4 (64 rows,
-// one wave per SIMD with the 192 x 64 Y^T accumulator in AGPRs -- half the LDS weight reads per row,
-// but measured 15% slower: one wave cannot hide the LDS / GELU latency the second wave covers)
-// NW = waves per block: 4 (two blocks per CU, each DMA-filling its own rings) or 8 (one block per CU:
-// each weight byte crosses into LDS once per CU; waves 0-3 fill the W1 ring, 4-7 the W2 ring)
+// TT = 16-row tiles per wave: 2 (32 rows, two waves per SIMD, accumulators in VGPRs; 4 measured 15% slower: one wave
+// per SIMD cannot hide the LDS / GELU latency the second wave covers)
+// NW = waves per block: 4 (two blocks per CU, each DMA-filling its own rings; 8 measured slower: 175.3 vs 162.8 us,
+// one block per CU: its waves hit the barriers in step)
 // CAP (with RES, bf16): the CrossAttentionPooler's tail (transformer.py:85-86) on its pooled tokens:
 //   o2 = O Wout^T + bo;  X <- LayerNorm(o2) g + b + (GELU(o2 W1^T + b0) W2^T + b3)
 // (the prologue's residual is the bias, its LayerNorm moves to the end beside the FFN, exact-erf GELU);
@@ -70,12 +69,12 @@ __device__ unsigned long long g_mr_all[MR_MAXB * 8 * (MR_NST + 2)];
   } while (0)
 #endif
 template <int TT, bool RES, int NW, bool F16, bool CAP = false>
-__global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : (TT == 2 ? 2 : 1)) void mlp_rows_kernel(void* __restrict__ Xv,
-                                                                       const void* __restrict__ W1v,
-                                                                       const void* __restrict__ W2v, int M, int Fh,
-                                                                       float eps, const void* __restrict__ Ov,
-                                                                       const void* __restrict__ Woutv,
-                                                                       const float* __restrict__ capb) {
+__global__ __launch_bounds__(64 * NW, 2) void mlp_rows_kernel(void* __restrict__ Xv, const void* __restrict__ W1v,
+                                                              const void* __restrict__ W2v, int M, int Fh, float eps,
+                                                              const void* __restrict__ Ov,
+                                                              const void* __restrict__ Woutv,
+                                                              const float* __restrict__ capb) {
+  static_assert(TT == 2 && NW == 4, "the ring fills and their vmcnt waits are written for four waves of 32 rows");
   static_assert(!CAP || (RES && !F16), "the CAP tail runs the bf16 prologue form");
   typedef typename Op16<F16>::t HT;  // operand element
   typedef typename Op16<F16>::x8 X8;
@@ -100,8 +99,6 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : (TT == 2 ? 2 : 1)) void mlp_
 #endif
   if constexpr (CAP)  // before any LDS-DMA: the compiler's own vmcnt waits cover these loads alone
     for (int i = tid; i < CAPL; i += 64 * NW) capl[i] = capb[i];
-  const int wg = wave & 3;                           // the wave's share of a ring fill
-  const bool gw1 = NW == 4 || wave < 4, gw2 = NW == 4 || wave >= 4;  // fills W1 / W2 pieces
   const int fr = lane & 15, fg = lane >> 4;
   const int64_t m0 = (int64_t)blockIdx.x * RROWS + wave * 16 * TT;
   const int nchunks = Fh / RHC;
@@ -121,26 +118,24 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : (TT == 2 ? 2 : 1)) void mlp_
   uint32_t o1[MP], o2[MP];
 #pragma unroll
   for (int j = 0; j < MP; ++j) {
-    const int q = (wg * MP + j) * 64 + lane;  // unit index inside a slot image
+    const int q = (wave * MP + j) * 64 + lane;  // unit index inside a slot image
     const int r1 = q / 24, u1 = (q % 24) ^ ((r1 >> 1) & 7);
     o1[j] = (uint32_t)(r1 * RE + u1 * 8) * 2;
     const int r2 = q >> 2, u2 = (q & 3) ^ ((r2 >> 2) & 2);
     o2[j] = (uint32_t)(r2 * Fh + u2 * 8) * 2;
   }
   auto dma_w1 = [&](int c, int slot) {  // W1 rows c*32 .. +31
-    if (!gw1) return;
     const HT* base = W1 + (int64_t)c * RHC * RE;
 #pragma unroll
     for (int j = 0; j < MP; ++j)
-      lds_dma16(o1[j], base, __builtin_amdgcn_readfirstlane(lds0 + slot * SLOT_B + (wg * MP + j) * 1024));
+      lds_dma16(o1[j], base, __builtin_amdgcn_readfirstlane(lds0 + slot * SLOT_B + (wave * MP + j) * 1024));
   };
   auto dma_w2 = [&](int c, int slot) {  // W2 columns c*32 .. +31 (permuted), all 192 rows
-    if (!gw2) return;
     const HT* base = W2p + c * RHC;
 #pragma unroll
     for (int j = 0; j < MP; ++j)
       lds_dma16(o2[j], base,
-                __builtin_amdgcn_readfirstlane(lds0 + W2RING + slot * SLOT_B + (wg * MP + j) * 1024));
+                __builtin_amdgcn_readfirstlane(lds0 + W2RING + slot * SLOT_B + (wave * MP + j) * 1024));
   };
   // fragment read offsets (bytes inside a slot): W1 row 16 ht + fr, unit 4 ks + fg; W2 row 16 o + fr, unit fg
   const int s1 = (fr >> 1) & 7;
@@ -200,17 +195,16 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : (TT == 2 ? 2 : 1)) void mlp_
       uint32_t ow[9];
 #pragma unroll
       for (int j = 0; j < 9; ++j) {
-        const int q = (wg * 9 + j) * 64 + lane, r = q / 24, u = (q % 24) ^ ((r >> 1) & 7);
+        const int q = (wave * 9 + j) * 64 + lane, r = q / 24, u = (q % 24) ^ ((r >> 1) & 7);
         ow[j] = (uint32_t)(r * RE + u * 8) * 2;
       }
 #pragma unroll
       for (int hf = 0; hf < 2; ++hf) {
         if (hf == 1 && !CAP) load_x();  // (program order: half 0, O, X, half 1 -- see the waits below)
-        if (NW == 4 || (wave >> 2) == hf)  // NW 8: waves 0-3 half 0, 4-7 half 1
 #pragma unroll
-          for (int j = 0; j < 9; ++j)
-            lds_dma16(ow[j], Wout + hf * 96 * RE,
-                      __builtin_amdgcn_readfirstlane(lds0 + hf * 3 * SLOT_B + (wg * 9 + j) * 1024));
+        for (int j = 0; j < 9; ++j)
+          lds_dma16(ow[j], Wout + hf * 96 * RE,
+                    __builtin_amdgcn_readfirstlane(lds0 + hf * 3 * SLOT_B + (wave * 9 + j) * 1024));
         if (hf == 0) {
           X8 ao[TT][RE / 32];
 #pragma unroll
@@ -252,8 +246,8 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : (TT == 2 ? 2 : 1)) void mlp_
     dma_w1(0, 0);
     if (nchunks > 1) dma_w1(1, 1);
     if (deep) dma_w1(2, 2);
-    // half 1 landed, the W1 fills may fly (NW 8: waves 0-3 hold no half-1 pieces, 4-7 no W1 fills)
-    if (deep && gw1) wait_vm(integral_constant<int, 3 * MP>{});
+    // half 1 landed, the W1 fills may fly
+    if (deep) wait_vm(integral_constant<int, 3 * MP>{});
     else wait_vm(integral_constant<int, 0>{});
     __syncthreads();
     outproj(integral_constant<int, 1>{});
@@ -302,8 +296,8 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : (TT == 2 ? 2 : 1)) void mlp_
           for (int i = 0; i < 4; ++i) y[f][tt][i] = fmaf((y[f][tt][i] - mu[tt]) * iv[tt], g[i], bb[i]);
       }
     }
-    // before H(0): W1(0) landed (newer: W1(1), W1(2), W2(0), W2(1); NW 8: each group its own two)
-    if (deep) wait_vm(integral_constant<int, (NW == 8 ? 2 : 4) * MP>{});
+    // before H(0): W1(0) landed (newer: W1(1), W1(2), W2(0), W2(1))
+    if (deep) wait_vm(integral_constant<int, 4 * MP>{});
     else wait_vm(integral_constant<int, 0>{});
   } else {
     dma_w1(0, 0);
@@ -314,8 +308,8 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : (TT == 2 ? 2 : 1)) void mlp_
     dma_w2(0, 0);
     if (deep) dma_w1(2, 2);
     if (nchunks > 1) dma_w2(1, 1);
-    // before H(0): W1(0) landed (newer: W1(1), W2(0), W1(2), W2(1); NW 8: W1(1), X, W1(2))
-    if (deep) wait_vm(integral_constant<int, (NW == 8 ? 2 : 4) * MP>{});
+    // before H(0): W1(0) landed (newer: W1(1), W2(0), W1(2), W2(1))
+    if (deep) wait_vm(integral_constant<int, 4 * MP>{});
     else wait_vm(integral_constant<int, 0>{});
   }
   __syncthreads();
@@ -323,9 +317,6 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : (TT == 2 ? 2 : 1)) void mlp_
 
   // GELU of one adjacent pair q (0 .. 4 TT - 1: tile tt, half ht, elements 2 (q & 1) + 0, 1) of a chunk's
   // H^T accumulators, packed into its bf16 B fragment for the down-projection
-#ifndef MLP_GELU16
-#define MLP_GELU16 3  // 3: gelu_tanh_h2x2_f32, 2: gelu_tanh_h2x2, 1: one pair per gelu_tanh_h2, 0: fp32 tanh form
-#endif
   auto gelu_pair = [&](auto qc, const f32x4 (&hs)[2][TT], X8 (&hb)[TT], int c) {
     constexpr int q = decltype(qc)::value, tt = q >> 2, ht = (q >> 1) & 1, i = 2 * (q & 1);
     HT2 pr;
@@ -333,7 +324,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : (TT == 2 ? 2 : 1)) void mlp_
       const float2_t bb = *(const float2_t*)(capl + RE + c * RHC + 16 * ht + 4 * fg + i);
       pr = __builtin_convertvector((float2_t){gelu_erf(hs[ht][tt][i] + bb[0]), gelu_erf(hs[ht][tt][i + 1] + bb[1])},
                                    HT2);
-    } else if constexpr (F16 && MLP_GELU16 == 3) {  // fp16 mode: pairs q, q + 1 from the fp32 accumulators
+    } else if constexpr (F16) {  // fp16 mode: pairs q, q + 1 (one tile row's four values) from the fp32 accumulators
       if constexpr ((q & 1) == 0) {
         f16x2_t a, b;
         gelu_tanh_h2x2_f32(hs[ht][tt][0], hs[ht][tt][1], hs[ht][tt][2], hs[ht][tt][3], a, b);
@@ -341,17 +332,6 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : (TT == 2 ? 2 : 1)) void mlp_
         hb[tt][4 * ht + 2] = b[0], hb[tt][4 * ht + 3] = b[1];
       }
       return;
-    } else if constexpr (F16 && MLP_GELU16 == 2) {  // fp16 mode: pairs q, q + 1 (one tile row's four values) at once
-      if constexpr ((q & 1) == 0) {
-        f16x2_t a = __builtin_convertvector((float2_t){hs[ht][tt][0], hs[ht][tt][1]}, f16x2_t);
-        f16x2_t b = __builtin_convertvector((float2_t){hs[ht][tt][2], hs[ht][tt][3]}, f16x2_t);
-        gelu_tanh_h2x2(a, b);
-        hb[tt][4 * ht + 0] = a[0], hb[tt][4 * ht + 1] = a[1];
-        hb[tt][4 * ht + 2] = b[0], hb[tt][4 * ht + 3] = b[1];
-      }
-      return;
-    } else if constexpr (F16 && MLP_GELU16) {  // fp16 mode: the pair's GELU in packed fp16 arithmetic
-      pr = gelu_tanh_h2(__builtin_convertvector((float2_t){hs[ht][tt][i], hs[ht][tt][i + 1]}, HT2));
     } else {
       pr = __builtin_convertvector((float2_t){gelu_tanh_fast(hs[ht][tt][i]), gelu_tanh_fast(hs[ht][tt][i + 1])}, HT2);
     }
@@ -370,10 +350,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : (TT == 2 ? 2 : 1)) void mlp_
     for (int i = 0; i < 2; ++i)
 #pragma unroll
       for (int tt = 0; tt < TT; ++tt) h[i][tt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#ifndef MLP_PU
-#define MLP_PU 2
-#endif
-    constexpr int PU = MLP_PU;  // k-steps of W1 fragments in flight ahead of their MFMAs
+    constexpr int PU = 2;  // k-steps of W1 fragments in flight ahead of their MFMAs
     X8 wa[PU][2];
 #pragma unroll
     for (int i = 0; i < PU; ++i)
@@ -437,10 +414,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : (TT == 2 ? 2 : 1)) void mlp_
     }
     // Y^T [192][32 rows] += W2c(perm) . GELU(H^T)
     {  // W2 fragments 4 tiles ahead of their MFMAs (fenced so the reads stay early; 3-6 measured)
-#ifndef MLP_PF
-#define MLP_PF 4
-#endif
-      constexpr int PF = MLP_PF;
+      constexpr int PF = 4;
       auto w2frag = [&](int o) { return *(const X8*)(ldsb + PAR * SLOT_B + o * 16 * 64 + f2); };
       X8 wb[PF];
 #pragma unroll
@@ -455,14 +429,9 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : (TT == 2 ? 2 : 1)) void mlp_
     }
     if (MORE) {
       // this thread's pieces of W1(c+2) and W2(c+1) landed; this chunk's own fills may still fly
-      if constexpr (NW == 8) {  // one matrix per wave
-        if (gw1 ? d1 : d2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(MP) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      } else {
-        if (d1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * MP) : "memory");
-        else if (d2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(MP) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
+      if (d1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * MP) : "memory");
+      else if (d2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(MP) : "memory");
+      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
     }
 #ifdef MMPFN_STAMPS_ALL
@@ -568,20 +537,16 @@ namespace {
 template <bool F16>
 hipError_t launch_mr(void* X, const void* W1perm, const void* W2perm, int64_t M, int Fh, float eps, hipStream_t st,
                      const void* O, const void* Wout) {
-#ifndef MLP_TT
-#define MLP_TT 2  // 4 measured slower: 202 vs 175 us per two-member launch
-#endif
-#ifndef MLP_NW
-#define MLP_NW 4  // 8 measured slower: 175.3 vs 162.8 us (one block per CU: its waves hit the barriers in step)
-#endif
-  constexpr int RROWS = 16 * MLP_NW * MLP_TT;
-  const dim3 grid((unsigned)((M + RROWS - 1) / RROWS)), block(64 * MLP_NW);
+  constexpr int TT = 2;  // 4 measured slower: 202 vs 175 us per two-member launch
+  constexpr int NW = 4;  // 8 measured slower: 175.3 vs 162.8 us (one block per CU: its waves hit the barriers in step)
+  constexpr int RROWS = 16 * NW * TT;
+  const dim3 grid((unsigned)((M + RROWS - 1) / RROWS)), block(64 * NW);
   if (O)
-    hipLaunchKernelGGL((mlp_rows_kernel<MLP_TT, true, MLP_NW, F16>), grid, block, 0, st, X, W1perm, W2perm, (int)M,
-                       Fh, eps, O, Wout, nullptr);
+    hipLaunchKernelGGL((mlp_rows_kernel<TT, true, NW, F16>), grid, block, 0, st, X, W1perm, W2perm, (int)M, Fh, eps, O,
+                       Wout, nullptr);
   else
-    hipLaunchKernelGGL((mlp_rows_kernel<MLP_TT, false, MLP_NW, F16>), grid, block, 0, st, X, W1perm, W2perm, (int)M,
-                       Fh, eps, nullptr, nullptr, nullptr);
+    hipLaunchKernelGGL((mlp_rows_kernel<TT, false, NW, F16>), grid, block, 0, st, X, W1perm, W2perm, (int)M, Fh, eps,
+                       nullptr, nullptr, nullptr);
   return hipGetLastError();
 }
 }  // namespace

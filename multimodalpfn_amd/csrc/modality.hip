@@ -25,22 +25,16 @@ namespace {
 // ---------------------------------------------------------------- big-tile GEMM (bf16)
 constexpr int TM = 256, TN = 256;
 static_assert(TM + TN == RING_ROWS, "one ring stage (tile_ring.h)");
-#ifndef GT_NST
-#define GT_NST 4  // 5 (all 160 KB of LDS): ViT batch 20.52-20.55 vs 20.21 ms, profiles/r04/modality/ab_gemm_tile_variants.txt
-#endif
-constexpr int TNST = GT_NST;                    // ring stages (4 x 32 KB: two slices in flight)
+// ring stages (4 x 32 KB: two slices in flight; 5, all 160 KB of LDS: ViT batch 20.52-20.55 vs 20.21 ms,
+// profiles/r04/modality/ab_gemm_tile_variants.txt)
+constexpr int TNST = 4;
 constexpr int TMT = TM / 32;                    // 16-row MFMA tiles per wave (8)
 constexpr int OST16 = TN + 8;                   // bf16 output staging row stride (elements)
 constexpr int OST32 = TN + 4;                   // fp32 output staging row stride (floats), 128 rows per pass
 constexpr int imax3(int a, int b, int c) { return a > b ? (a > c ? a : c) : (b > c ? b : c); }
 constexpr int GT_LDS = imax3(TNST * RING_STAGE, TM * OST16 * 2, (TM / 2) * OST32 * 4);
 
-#ifndef GT_GM
-#define GT_GM 4  // super-tile (M tiles x N tiles) of the block order
-#endif
-#ifndef GT_GN
-#define GT_GN 8
-#endif
+constexpr int GT_GM = 4, GT_GN = 8;  // super-tile (M tiles x N tiles) of the block order
 
 // C = A[M][K] . W[N][K]^T, 256 x 256 tile per 512-thread block (8 waves as 2 x 4, each 128 x 64 =
 // 8 x 4 MFMA-16 tiles).  K moves in 32-wide slices through the 4-stage LDS ring of tile_ring.h (slices
@@ -249,9 +243,7 @@ typedef short a64_s4 __attribute__((ext_vector_type(4)));
 
 // NCH query chains of 32 per wave (block = 4 waves x 32 NCH queries): with two, one chain's exps issue
 // beside the other chain's MFMAs inside one basic block (the per-chain lazy rescales are decided before it)
-#ifndef A64_NCH
-#define A64_NCH 2
-#endif
+constexpr int A64_NCH = 2;
 template <int NCH>
 __global__ __launch_bounds__(256, 2) void attn64_kernel(const bf16* __restrict__ qkv, const float* __restrict__ kbias,
                                                         bf16* __restrict__ out, int L, int H, int q0, int nq,

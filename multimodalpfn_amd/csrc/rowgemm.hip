@@ -169,12 +169,10 @@ constexpr int OVST = 32 + 8;    // V^T tile row stride (bf16): 80 B
 constexpr int OWEL = QC * OVST; // per-wave staging elements (>= 32 * OQST)
 static_assert(32 * OQST <= OWEL, "Q/K staging tile must fit");
 
-// QKB: Q / K stored in bf16 whatever the operand type (the fp16 mode's forward: its attention runs S on bf16 MFMA)
-template <bool F16, bool QKB>
+// Q / K are stored in bf16 whatever the operand type (the fp16 mode's forward: its attention runs S on bf16 MFMA)
+template <bool F16>
 __device__ __forceinline__ void qkv2_tile(const RgArgs& p, int tiles_per_b, int bid, uint16_t* Ws) {
-  typedef typename Op16<F16 && !QKB>::t OT;  // Q / K element
   typedef typename Op16<F16>::x8 X8;
-  typedef typename Op16<F16 && !QKB>::x4 X4;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int fr = lane & 15, fg = lane >> 4;
   const int rd = (int)p.a_rdiv;
@@ -253,10 +251,10 @@ __device__ __forceinline__ void qkv2_tile(const RgArgs& p, int tiles_per_b, int 
         for (int tt = 0; tt < 2; ++tt)
   #pragma unroll
           for (int f = 0; f < QC / 16; ++f) {
-            X4 o;
-            o[0] = (OT)acc[f][tt][0], o[1] = (OT)acc[f][tt][1];
-            o[2] = (OT)acc[f][tt][2], o[3] = (OT)acc[f][tt][3];
-            *(X4*)(Os + (tt * 16 + fr) * OQST + f * 16 + fg * 4) = o;
+            bf16x4 o;
+            o[0] = (bf16)acc[f][tt][0], o[1] = (bf16)acc[f][tt][1];
+            o[2] = (bf16)acc[f][tt][2], o[3] = (bf16)acc[f][tt][3];
+            *(bf16x4*)(Os + (tt * 16 + fr) * OQST + f * 16 + fg * 4) = o;
           }
         uint16_t* base = j == 0 ? (uint16_t*)p.q + (((int64_t)b * p.H + h0) * p.S + pos0) * 32
                                 : (uint16_t*)p.k + (((int64_t)b * p.H + h0) * p.Npad + pos0) * 32;
@@ -301,22 +299,19 @@ __device__ __forceinline__ void qkv2_tile(const RgArgs& p, int tiles_per_b, int 
       __syncthreads();
     }
   };
-#ifndef QKV_VERSIONED
-#define QKV_VERSIONED 1
-#endif
-  if (QKV_VERSIONED && full) run(std::true_type{});
+  if (full) run(std::true_type{});
   else run(std::false_type{});
 }
 
 // Two row sets in one launch: blocks [0, nblk1) project p's rows (the train rows: q|k|v), the
 // rest p2's (the test rows: q only, a third of the chunks) -- the short test-row blocks run last
 // and fill the grid's tail instead of a separate under-filled launch.
-template <bool F16, bool QKB>
+template <bool F16>
 __global__ __launch_bounds__(256, 2) void rowgemm_qkv2_kernel(const RgArgs p, int tiles_per_b, const RgArgs p2,
                                                               int tiles2, int nblk1) {
   __shared__ __attribute__((aligned(16))) uint16_t Ws[2 * QCEL + 4 * OWEL];
-  if ((int)blockIdx.x < nblk1) qkv2_tile<F16, QKB>(p, tiles_per_b, blockIdx.x, Ws);
-  else qkv2_tile<F16, QKB>(p2, tiles2, blockIdx.x - nblk1, Ws);
+  if ((int)blockIdx.x < nblk1) qkv2_tile<F16>(p, tiles_per_b, blockIdx.x, Ws);
+  else qkv2_tile<F16>(p2, tiles2, blockIdx.x - nblk1, Ws);
 }
 
 // C[m] = (LN? LayerNorm(A[m]) : A[m]) . W^T + bias, A fp32 [M][192], W [N][192] bf16, C bf16 [M][N]
@@ -553,19 +548,15 @@ hipError_t qkv_rowset(const void* X, const RowSet& s, void* q, void* k, void* vt
   nblk = (int64_t)tiles * (s.M / s.rdiv);
   return hipSuccess;
 }
-// fp32 state: bf16 Q / K; fp16 state: fp16 or bf16 Q / K
-bool qkv_types_ok(DType x_t, DType qk_t) {
-  return x_t == DType::F32 ? qk_t == DType::BF16 : x_t == DType::F16 && qk_t != DType::F32;
-}
 }  // namespace
 
 hipError_t launch_rowgemm_qkv(const void* X, const RowSet* sets, int nset, void* q, void* k, void* vt, int S, int Npad,
-                              int H, hipStream_t st, DType x_t, DType qk_t) {
+                              int H, hipStream_t st, DType x_t) {
   RgArgs a1, a2;
   int t1, t2;
   int64_t n1, n2 = 0;
-  if (nset < 1 || nset > 2 || !qkv_types_ok(x_t, qk_t)) return hipErrorInvalidValue;
-  const bool f16 = x_t == DType::F16, qk_bf16 = qk_t == DType::BF16;
+  if (nset < 1 || nset > 2 || x_t == DType::BF16) return hipErrorInvalidValue;
+  const bool f16 = x_t == DType::F16;
   hipError_t e = qkv_rowset(X, sets[0], q, k, vt, S, Npad, H, a1, t1, n1);
   if (e != hipSuccess) return e;
   if (nset == 2) {
@@ -577,9 +568,8 @@ hipError_t launch_rowgemm_qkv(const void* X, const RowSet* sets, int nset, void*
   }
   if (n1 + n2 == 0) return hipSuccess;
   const dim3 g((unsigned)(n1 + n2));
-  if (f16 && qk_bf16) hipLaunchKernelGGL((rowgemm_qkv2_kernel<true, true>), g, dim3(256), 0, st, a1, t1, a2, t2, (int)n1);
-  else if (f16) hipLaunchKernelGGL((rowgemm_qkv2_kernel<true, false>), g, dim3(256), 0, st, a1, t1, a2, t2, (int)n1);
-  else hipLaunchKernelGGL((rowgemm_qkv2_kernel<false, false>), g, dim3(256), 0, st, a1, t1, a2, t2, (int)n1);
+  if (f16) hipLaunchKernelGGL(rowgemm_qkv2_kernel<true>, g, dim3(256), 0, st, a1, t1, a2, t2, (int)n1);
+  else hipLaunchKernelGGL(rowgemm_qkv2_kernel<false>, g, dim3(256), 0, st, a1, t1, a2, t2, (int)n1);
   return hipGetLastError();
 }
 

@@ -111,9 +111,6 @@ DEFAULT_BATCH = int(os.environ.get("MMPFN_BATCH", "1"))  # members per batched f
 # 1: the forwards run their last layer in full instead of pruned to the rows the decoder reads (the
 # same logits bit for bit -- the pruned form's reference and A/B handle)
 DEFAULT_FULL_LAST_LAYER = os.environ.get("MMPFN_FULL_LAST_LAYER") == "1"
-_DEBUG_SYNC = os.environ.get("MMPFN_DEBUG_SYNC") == "1"  # diagnostics: serialise forward_many's units
-_DEBUG_KEEP = os.environ.get("MMPFN_DEBUG_KEEP") == "1"  # diagnostics: keep every prepared input alive
-_KEEP: list = []
 _SERIAL = itertools.count(1)  # engine serial numbers: cache tags that a freed engine's id() could alias
 
 
@@ -253,8 +250,6 @@ class HipEngine:
         # a value target has no class codes: nothing to compute or upload (the engine ignores uniq / U)
         uniq = None if self.cfg.is_regression else self._dev(torch.from_numpy(target_uniques(y_np)))
         yd = self._dev(torch.from_numpy(y_np))
-        if _DEBUG_KEEP:
-            _KEEP.append((xd, td, yd, uniq))
         return xd, td, yd, uniq, S, F, C, N, G
 
     def forward(self, x, tokens, y_train, precision: int, check_nan: bool = True) -> torch.Tensor:
@@ -428,8 +423,6 @@ class HipEngine:
                 with torch.cuda.stream(streams[k]):
                     self._check(self.lib.mmpfn_select_lane(self.ctx, k), "mmpfn_select_lane")
                     run(unit, streams[k])
-                    if _DEBUG_SYNC:
-                        torch.cuda.synchronize(self.device)
             launched += 1
 
         pending: dict = {}  # geometry -> member indices waiting for a full unit

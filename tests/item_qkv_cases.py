@@ -16,7 +16,7 @@ The restatement (``project``) is float64 arithmetic that rounds only where the m
                   fl32(log2(e) / sqrt(32)) (weight_pack.h ``prescale_item_q``; ``feat_block_cases.C32``); fp32
                   accumulation; Q, K, V^T stored in bf16.
   mode 5 (fp16)   X is fp16 already (the state), W to fp16 after the same prescale; Q, K and V^T stored in bf16 all the
-                  same (capi.cpp ``MMPFN_F16_QK_BF16``).  At T > 64 it is mode 1 (``decode_prec``).
+                  same (the item attention's S runs on bf16 MFMA in every 16-bit mode).  At T > 64 it is mode 1 (``decode_prec``).
   mode 0 (fp32)   W split as weight_pack.h ``split_bf16`` splits it, hi = bf16(w), lo = bf16(w - hi); X split the same
                   way in registers (rowgemm3.hip ``split_rows3``); three products per element, w_lo x_hi + w_hi x_lo +
                   w_hi x_hi, the lo x lo one dropped; q not prescaled; fp32 stores.

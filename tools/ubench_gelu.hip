@@ -1,7 +1,7 @@
 // Microbenchmark (diagnostic tool): the MLP chunk's GELU forms in the chunk's MFMA mix (mlp_rows.hip, fp16 mode)
 // without memory.  Per chunk and wave: 48 v_mfma_f32_16x16x32_f16 (up- and down-projection of 32 hidden x 32 rows
 // x 192 features) and the previous chunk's GELU on 16 fp32 accumulator values per lane, packed into fp16 B fragments.
-// GELU forms: 0 none; 1 tanh form in packed fp16 (gelu_tanh_h2, today's); 2 tanh form in fp32 (gelu_tanh_fast);
+// GELU forms: 0 none; 1 tanh form in packed fp16 (gelu_tanh_h2x2_f32, today's); 2 tanh form in fp32 (gelu_tanh_fast);
 // 3 exact-erf GELU as x * (1/2 + t P(t^2)), t = clamp(x / 4.5, -1, 1), P of degree 8 in packed fp32
 // (v_pk_fma_f32), no transcendental; 4 form 3 with the clamp folded into one v_med3 per element.
 // Build: hipcc -O3 --offload-arch=gfx950 -mllvm -amdgpu-mfma-vgpr-form=1 tools/ubench_gelu.hip -o tools/ubench_gelu
@@ -24,8 +24,7 @@ __device__ __forceinline__ f2 gelu_poly2(f2 x) {
 
 template <int G>
 __device__ __forceinline__ f16x2_t gelu2(float a, float b) {
-  if constexpr (G == 1) return gelu_tanh_h2(f16x2_t{(_Float16)a, (_Float16)b});
-  else if constexpr (G == 2) return f16x2_t{(_Float16)gelu_tanh_fast(a), (_Float16)gelu_tanh_fast(b)};
+  if constexpr (G == 2) return f16x2_t{(_Float16)gelu_tanh_fast(a), (_Float16)gelu_tanh_fast(b)};
   else {
     const f2 g = gelu_poly2(f2{a, b});
     return f16x2_t{(_Float16)g[0], (_Float16)g[1]};
@@ -46,7 +45,16 @@ __global__ __launch_bounds__(256, 2) void kern(float* out, int iters) {
   f16x8 hb[2];
   for (int j = 0; j < 8; ++j) hb[0][j] = (_Float16)(0.1f * j), hb[1][j] = (_Float16)(0.2f * j + 0.05f);
   for (int it = 0; it < iters; ++it) {
-    if constexpr (G != 0) {
+    if constexpr (G == 1) {  // two pairs (one tile row's four values) per block
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          f16x2_t va, vb;
+          gelu_tanh_h2x2_f32(h16[t][j][0], h16[t][j][1], h16[t][j][2], h16[t][j][3], va, vb);
+          hb[t][4 * j] = va[0], hb[t][4 * j + 1] = va[1], hb[t][4 * j + 2] = vb[0], hb[t][4 * j + 3] = vb[1];
+        }
+    } else if constexpr (G != 0) {
 #pragma unroll
       for (int t = 0; t < 2; ++t)
 #pragma unroll

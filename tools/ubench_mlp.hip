@@ -2,7 +2,7 @@
 // 32x32x16 MFMA form (half the MFMA issue holds of 16x16x32 for the same flops) run a chunk faster at two waves per
 // SIMD?  Per chunk and wave: the up-projection (32 hidden x 32 rows x 192) and the down-projection (192 x 32 rows x
 // 32 hidden) = 48 v_mfma_f32_16x16x32_f16 or 24 v_mfma_f32_32x32x16_f16, the previous chunk's GELU on 16 values
-// per lane in packed fp16 (gelu_tanh_h2: 2 transcendentals per value), and 24 ds_read_b128 of weight fragments.
+// per lane in packed fp16 (the tanh form of common.h gelu_tanh_h2x2_f32: 2 transcendentals per value), and 24 ds_read_b128 of weight fragments.
 // Build: hipcc -O3 --offload-arch=gfx950 -mllvm -amdgpu-mfma-vgpr-form=1 tools/ubench_mlp.hip -o tools/ubench_mlp
 #include <hip/hip_runtime.h>
 #include <stdio.h>
