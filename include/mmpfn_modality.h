@@ -69,6 +69,41 @@ int mmpfn_enc_finalize(mmpfn_enc* enc); /* pack / convert / upload; synchronous 
 int mmpfn_vit_forward(mmpfn_enc* enc, const float* images, int B, int H, int W, float* cls, float* tokens,
                       int precision);
 
+/* Raw pixels (SURVEY.md 8(f)4').  The reference resizes every decoded picture on the host in front of its image
+ * tower (mmpfn/datasets/pad_ufes_20.py:53-61, cbis_ddsm.py:71-81, petfinder.py:85-95):
+ *     img = np.array(img.convert("RGB").resize((img_size, img_size), Image.BILINEAR), dtype=np.float32)
+ *     images /= 255.0
+ * The calls below take the RGB uint8 pixels as decoded, at whatever size each image has, and do that resize on the
+ * device bit for bit as Pillow's 8-bit path does it: 22-bit fixed-point coefficients built on the host in double
+ * (the formula: csrc/img_coeffs.h), horizontal pass first, uint8 between the passes, then float32(v) / float32(255).
+ * Input: pixels = device buffer of packed images, image b = uint8 [H_b][W_b][3] at byte offsets[b]; offsets [B]
+ * int64 and sizes [B][2] int32 = (H_b, W_b) are host arrays.  Refused with MMPFN_ERR_INVALID: an empty image, a
+ * side over 16384, H > 100 * W (beyond that aspect Pillow's own result equals the vertical-first order; the order
+ * is not guessed), oh / ow not a multiple of the patch, a patch over 16. */
+
+/* One axis of that resize, in_size -> out_size (each 1 .. 16384): k [out_size][*ksize] int32 coefficients (zero
+ * past an index's count), bounds [out_size][2] = (first source index, count).  With k == NULL only *ksize is
+ * returned.  Host only: needs no GPU and no context. */
+int mmpfn_resize_coeffs(int in_size, int out_size, int32_t* k, int32_t* bounds, int* ksize);
+
+/* The 256 values a byte becomes: out[v] = float32(v) / float32(255).  Host only. */
+int mmpfn_pixel_scale_table(float* out);
+
+/* Kernel tap (tests, diagnostics): the image front end alone, on the encoder's stream; needs no model.
+ * resized (optional) uint8 [B][oh][ow][3] = Pillow's resize; patches (optional, 16-byte aligned)
+ * [B * (oh / patch) * (ow / patch)][kpad] = the patch-embedding GEMM's A operand: row (b, py, px), column
+ * c * patch^2 + ky * patch + kx, zero from 3 * patch^2 to kpad (kpad % 32 == 0); fp32 for MMPFN_PREC_F32, bf16
+ * for MMPFN_PREC_BF16.  All of resized, patches are device buffers; at least one is required. */
+int mmpfn_image_patches_rgb(mmpfn_enc* enc, const uint8_t* pixels, const int64_t* offsets, const int32_t* sizes,
+                            int B, int oh, int ow, int patch, int kpad, uint8_t* resized, void* patches,
+                            int precision);
+
+/* The ViT forward from raw pixels: the front end above writes the patch GEMM's A operand, then everything
+ * the fp32-image entry point does after its im2col (the same values as that call on the resized images / 255).
+ * oh, ow multiples of the patch; the model must have in_chans == 3; cls / tokens as above for oh x ow images. */
+int mmpfn_vit_forward_rgb(mmpfn_enc* enc, const uint8_t* pixels, const int64_t* offsets, const int32_t* sizes, int B,
+                          int oh, int ow, float* cls, float* tokens, int precision);
+
 /* ElectraModel.forward(input_ids, attention_mask, token_type_ids) (transformers modeling_electra):
  * ids / mask / types [B][L] int32 (mask, types may be NULL: all ones / zeros; mask 0 excludes the
  * key), cls [B][dim] fp32 = last_hidden_state[:, 0]; hidden (optional) [B][L][dim] fp32 =

@@ -175,6 +175,10 @@ MODALITY_SIGNATURES = [
     ("mmpfn_enc_load_weight", _i, [_vp, ctypes.c_char_p, _vp, _i64]),
     ("mmpfn_enc_finalize", _i, [_vp]),
     ("mmpfn_vit_forward", _i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i]),
+    ("mmpfn_resize_coeffs", _i, [_i, _i, _vp, _vp, ctypes.POINTER(ctypes.c_int)]),
+    ("mmpfn_pixel_scale_table", _i, [_vp]),
+    ("mmpfn_image_patches_rgb", _i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i]),
+    ("mmpfn_vit_forward_rgb", _i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i]),
     ("mmpfn_text_forward", _i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i]),
     ("mmpfn_enc_attention", _i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i]),
     ("mmpfn_enc_linear", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),

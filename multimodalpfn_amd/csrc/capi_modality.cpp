@@ -6,6 +6,8 @@
 //   im2col + GEMM (patch_embed)  -> [cls | patches] + interpolated pos_embed
 //   -> depth x [X += ls1 * proj(attn(qkv(LN1 X)));  X += ls2 * fc2(GELU(fc1(LN2 X)))]
 //   -> norm; x_norm_clstoken = row 0.
+// From raw pixels (mmpfn_vit_forward_rgb) the im2col is the image front end's (imgprep.hip): Pillow's bilinear
+// resize with host-built integer tables (img_coeffs.h), then the same GEMM and everything after it.
 // Text (transformers ElectraModel: ElectraEmbeddings, then BERT-style post-LN layers):
 //   LN(word + type + pos) [-> embeddings_project]
 //   -> depth x [X = LN1(X + dense(attn(qkv X)));  X = LN2(X + out(GELU(inter X)))]
@@ -16,6 +18,7 @@
 // State: X [B * L][dim] fp32 (residual stream), GEMM operands in the compute dtype.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <map>
@@ -25,6 +28,7 @@
 
 #include "../../include/mmpfn_modality.h"
 #include "devbuf.h"
+#include "img_coeffs.h"
 #include "modality.h"
 
 using namespace mmpfn;
@@ -36,6 +40,28 @@ struct EncLayer {
   DevBuf ln1g, ln1b, ln2g, ln2b, ls1, ls2;
   Weight qkv, proj, fc1, fc2;  // fp32 and bf16, both natural [N][K]
   DevBuf qkv_b, proj_b, fc1_b, fc2_b;
+};
+
+// one axis of the image front end's resize, as img_coeffs.h builds it
+struct ResizeTable {
+  int ksize = 0;
+  std::vector<int32_t> k, bounds;
+};
+
+// pinned host staging of the front end's per-batch upload; `ev` marks the last copy that read it
+struct PinnedStage {
+  void* p = nullptr;
+  size_t bytes = 0;
+  hipEvent_t ev = nullptr;
+  bool pending = false;
+  PinnedStage() = default;
+  PinnedStage(const PinnedStage&) = delete;
+  PinnedStage& operator=(const PinnedStage&) = delete;
+  ~PinnedStage() {  // teardown: an error here has no caller to report to
+    if (pending) (void)hipEventSynchronize(ev);
+    if (p) (void)hipHostFree(p);
+    if (ev) (void)hipEventDestroy(ev);
+  }
 };
 
 }  // namespace
@@ -55,6 +81,12 @@ struct mmpfn_enc {
   DevBuf wemb, pemb, temb, emb_g, emb_b, eproj_b;
   // workspace
   DevBuf X, A, QKV, O, Hh, Y, Xc, Ac, Oc, Hc, Yc, kb, flag, P0;
+  // image front end: host tables per (in, out) size, the batch's descriptors + tables on the device, the 256
+  // scaled pixel values
+  std::map<std::pair<int, int>, ResizeTable> rz_cache;
+  PinnedStage rz_host[2];  // alternating: packing a batch does not wait for the copy of the one before
+  DevBuf rz_dev[2], rz_lut;
+  int rz_slot = 0;
 };
 
 namespace {
@@ -281,6 +313,169 @@ int cls_tail(mmpfn_enc* enc, const EncLayer& Lw, int B, int64_t L, int prec, boo
   return MMPFN_OK;
 }
 
+// workspace of a ViT forward of B images of H x W (multiples of the patch)
+int vit_workspace(mmpfn_enc* enc, int B, int H, int W, int prec) {
+  const int P = enc->d.patch;
+  const int64_t M = (int64_t)B * (1 + (int64_t)(H / P) * (W / P));
+  if (M > 0x7fffffffll) return fail(enc, MMPFN_ERR_INVALID, "batch too large");
+  HIPCHK(hipSetDevice(enc->device));
+  return ensure_ws(enc, M, B, prec);
+}
+
+// DinoVisionTransformer.forward_features from the patch-embedding GEMM on: enc->A holds the im2col rows
+// [B * np][Kpad] of B images of H x W in the compute dtype (launch_im2col's or the image front end's)
+int vit_from_patches(mmpfn_enc* enc, int B, int H, int W, float* cls, float* tokens, int prec) {
+  const auto& d = enc->d;
+  const int P = d.patch, D = d.dim, F = d.mlp_hidden, nh = d.heads;
+  const bool bf = prec == PREC_BF16;
+  const int gh = H / P, gw = W / P, np = gh * gw;
+  const int64_t L = 1 + np, M = (int64_t)B * L;
+  const float eps = d.ln_eps;
+  hipStream_t st = enc->stream;
+  RC(ensure(enc, enc->P0, (size_t)B * np * D * 4));
+  const float* pe = nullptr;
+  RC(pos_for(enc, gh, gw, &pe));
+  // patch embedding: GEMM (+ bias) -> [cls | patches] + pos
+  RC(linear(enc, prec, enc->A.p, enc->pe_w, enc->pe_b, B * np, D, enc->Kpad, GT_F32, 0, enc->P0.p, nullptr, nullptr));
+  float* X = (float*)enc->X.p;
+  HIPCHK(launch_vit_assemble((const float*)enc->P0.p, (const float*)enc->cls_tok.p, pe, B, np, D, X, st));
+  for (int i = 0; i < d.depth; ++i) {
+    const EncLayer& Lw = enc->layers[i];
+    const bool tail = i == d.depth - 1 && tokens == nullptr;
+    // X += ls1 * attn(norm1(X))   (block.py:106-115)
+    HIPCHK(launch_ln_dual(X, M, D, eps, bf ? nullptr : (float*)enc->A.p, bf ? enc->A.p : nullptr,
+                          (const float*)Lw.ln1g.p, (const float*)Lw.ln1b.p, st));
+    RC(linear(enc, prec, enc->A.p, Lw.qkv, Lw.qkv_b, (int)M, 3 * D, D, GT_BF16, 0, enc->QKV.p, nullptr, nullptr));
+    if (tail) {
+      HIPCHK(launch_attn64(enc->QKV.p, nullptr, enc->Oc.p, B, (int)L, nh, 0, 1, 1, prec, st));
+      RC(cls_tail(enc, Lw, B, L, prec, false));
+      break;
+    }
+    HIPCHK(launch_attn64(enc->QKV.p, nullptr, enc->O.p, B, (int)L, nh, 0, (int)L, L, prec, st));
+    RC(linear(enc, prec, enc->O.p, Lw.proj, Lw.proj_b, (int)M, D, D, GT_RESID, 0, X,
+              (const float*)Lw.ls1.p, (float*)enc->Y.p));
+    // X += ls2 * mlp(norm2(X))
+    HIPCHK(launch_ln_dual(X, M, D, eps, bf ? nullptr : (float*)enc->A.p, bf ? enc->A.p : nullptr,
+                          (const float*)Lw.ln2g.p, (const float*)Lw.ln2b.p, st));
+    RC(linear(enc, prec, enc->A.p, Lw.fc1, Lw.fc1_b, (int)M, F, D, GT_BF16, 1, enc->Hh.p, nullptr, nullptr));
+    RC(linear(enc, prec, enc->Hh.p, Lw.fc2, Lw.fc2_b, (int)M, D, F, GT_RESID, 0, X,
+              (const float*)Lw.ls2.p, (float*)enc->Y.p));
+  }
+  // x_norm = norm(x); x_norm_clstoken = x_norm[:, 0]
+  if (tokens) {
+    HIPCHK(launch_ln_dual(X, M, D, eps, tokens, nullptr, (const float*)enc->norm_g.p, (const float*)enc->norm_b.p, st));
+    HIPCHK(launch_gather_rows(tokens, L * D, B, D, cls, 4, st));
+  } else {
+    HIPCHK(launch_ln_dual((const float*)enc->Xc.p, B, D, eps, cls, nullptr, (const float*)enc->norm_g.p,
+                          (const float*)enc->norm_b.p, st));
+  }
+  return MMPFN_OK;
+}
+
+// the table of one axis, built on first use
+const ResizeTable& resize_table(mmpfn_enc* enc, int in_size, int out_size) {
+  ResizeTable& t = enc->rz_cache[std::make_pair(in_size, out_size)];
+  if (t.ksize == 0) {
+    t.ksize = resize_ksize(in_size, out_size);
+    t.k.resize((size_t)out_size * t.ksize);
+    t.bounds.resize((size_t)out_size * 2);
+    resize_coeffs(in_size, out_size, t.k.data(), t.bounds.data());
+  }
+  return t;
+}
+
+// The image front end on the encoder's stream: checks, the batch's descriptors and coefficient tables (cached on
+// the host per (in, out), packed into pinned memory, one upload), then the kernel.
+int image_front(mmpfn_enc* enc, const uint8_t* pixels, const int64_t* offsets, const int32_t* sizes, int B, int oh,
+                int ow, int P, int kpad, uint8_t* resized, void* patches, int prec) {
+  if (B <= 0 || B > 65535 || !pixels || !offsets || !sizes)
+    return fail(enc, MMPFN_ERR_INVALID, "pixels, offsets, sizes and 0 < B <= 65535 are required");
+  if (P <= 0 || P > IMGPREP_PMAX)
+    return fail(enc, MMPFN_ERR_INVALID, "the raw-pixel path needs a patch size of at most " + std::to_string(IMGPREP_PMAX));
+  if (oh <= 0 || ow <= 0 || oh % P || ow % P || oh > RESIZE_MAX_SIDE || ow > RESIZE_MAX_SIDE)
+    return fail(enc, MMPFN_ERR_INVALID, "oh and ow must be positive multiples of the patch size, at most 16384");
+  if (kpad < 3 * P * P || kpad % 32)
+    return fail(enc, MMPFN_ERR_INVALID, "kpad must be a multiple of 32 and at least 3 * patch * patch");
+  if ((uintptr_t)patches & 15) return fail(enc, MMPFN_ERR_INVALID, "patches must be 16-byte aligned");
+  int max_w = 0;
+  for (int b = 0; b < B; ++b) {
+    const int H = sizes[2 * b], W = sizes[2 * b + 1];
+    const std::string which = "image " + std::to_string(b) + " (" + std::to_string(H) + " x " + std::to_string(W) + ")";
+    if (H <= 0 || W <= 0) return fail(enc, MMPFN_ERR_INVALID, which + " is empty");
+    if (H > RESIZE_MAX_SIDE || W > RESIZE_MAX_SIDE) return fail(enc, MMPFN_ERR_INVALID, which + " has a side over 16384");
+    // beyond this aspect Pillow's result equals the vertical-first order: refused, not guessed
+    if ((int64_t)H > 100ll * W) return fail(enc, MMPFN_ERR_INVALID, which + " is taller than 100 times its width (H > 100 * W)");
+    if (offsets[b] < 0) return fail(enc, MMPFN_ERR_INVALID, which + " has a negative offset");
+    max_w = std::max(max_w, W);
+  }
+  if (enc->rz_cache.size() > 4096) enc->rz_cache.clear();
+  // layout (int32 units from the descriptors' end): per distinct (in, out) of the batch, k then bounds
+  std::map<std::pair<int, int>, int64_t> at;
+  int64_t words = 0;
+  auto place = [&](int in_size, int out_size) {
+    auto key = std::make_pair(in_size, out_size);
+    auto it = at.find(key);
+    if (it != at.end()) return it->second;
+    const ResizeTable& t = resize_table(enc, in_size, out_size);
+    const int64_t o = words;
+    words += (int64_t)t.k.size() + (int64_t)t.bounds.size();
+    at.emplace(key, o);
+    return o;
+  };
+  std::vector<ImgPrepDesc> desc(B);
+  int max_ksh = 0;
+  for (int b = 0; b < B; ++b) {
+    const int H = sizes[2 * b], W = sizes[2 * b + 1];
+    const int64_t ho = place(W, ow), vo = place(H, oh);
+    if (words > 0x7fffffffll) return fail(enc, MMPFN_ERR_INVALID, "the batch's resize tables are too large");
+    const ResizeTable& th = resize_table(enc, W, ow);
+    const ResizeTable& tv = resize_table(enc, H, oh);
+    ImgPrepDesc& e = desc[b];
+    e.pix_off = offsets[b], e.H = H, e.W = W;
+    e.kh = (int32_t)ho, e.hb = (int32_t)(ho + (int64_t)th.k.size()), e.ksh = th.ksize;
+    e.kv = (int32_t)vo, e.vb = (int32_t)(vo + (int64_t)tv.k.size()), e.ksv = tv.ksize;
+    max_ksh = std::max(max_ksh, th.ksize);
+  }
+  const size_t dbytes = (size_t)B * sizeof(ImgPrepDesc), bytes = dbytes + (size_t)words * 4;
+  enc->rz_slot ^= 1;
+  PinnedStage& hs = enc->rz_host[enc->rz_slot];
+  DevBuf& dv = enc->rz_dev[enc->rz_slot];
+  if (!hs.ev) HIPCHK(hipEventCreateWithFlags(&hs.ev, hipEventDisableTiming));
+  if (hs.pending) {  // the copy of two batches ago may still read this staging memory
+    HIPCHK(hipEventSynchronize(hs.ev));
+    hs.pending = false;
+  }
+  if (hs.bytes < bytes) {
+    if (hs.p) HIPCHK(hipHostFree(hs.p));
+    hs.p = nullptr, hs.bytes = 0;
+    const size_t cap = std::max(bytes + bytes / 2, (size_t)1 << 16);
+    HIPCHK(hipHostMalloc(&hs.p, cap, hipHostMallocDefault));
+    hs.bytes = cap;
+  }
+  std::memcpy(hs.p, desc.data(), dbytes);
+  int32_t* tw = (int32_t*)((char*)hs.p + dbytes);
+  for (const auto& kv : at) {
+    const ResizeTable& t = enc->rz_cache[kv.first];
+    std::memcpy(tw + kv.second, t.k.data(), t.k.size() * 4);
+    std::memcpy(tw + kv.second + t.k.size(), t.bounds.data(), t.bounds.size() * 4);
+  }
+  if (!enc->rz_lut.p) {
+    std::vector<float> lut(256);
+    pixel_scale_table(lut.data());
+    RC(upload(enc, enc->rz_lut, lut));
+  }
+  RC(ensure(enc, dv, bytes));
+  hipStream_t st = enc->stream;
+  HIPCHK(hipMemcpyAsync(dv.p, hs.p, bytes, hipMemcpyHostToDevice, st));
+  HIPCHK(hipEventRecord(hs.ev, st));
+  hs.pending = true;
+  const hipError_t e = launch_imgprep(pixels, (const ImgPrepDesc*)dv.p,
+                                      (const int32_t*)((const char*)dv.p + dbytes), (const float*)enc->rz_lut.p,
+                                      B, max_w, max_ksh, oh, ow, P, kpad, resized, patches, prec != PREC_BF16, st);
+  HIPCHK(e);
+  return MMPFN_OK;
+}
+
 int check_desc(mmpfn_enc* enc, const mmpfn_enc_desc& d) {
   if (d.kind != MMPFN_ENC_VIT && d.kind != MMPFN_ENC_TEXT) return fail(enc, MMPFN_ERR_INVALID, "unknown encoder kind");
   if (d.dim <= 0 || d.heads <= 0 || d.dim != 64 * d.heads)
@@ -357,58 +552,51 @@ int mmpfn_vit_forward(mmpfn_enc* enc, const float* images, int B, int H, int W, 
   if (!enc) return MMPFN_ERR_INVALID;
   if (!enc->finalized || enc->d.kind != MMPFN_ENC_VIT) return fail(enc, MMPFN_ERR_STATE, "no finalized ViT model");
   const auto& d = enc->d;
-  const int P = d.patch, D = d.dim, F = d.mlp_hidden, nh = d.heads;
-  if (B <= 0 || !images || !cls || H <= 0 || W <= 0 || H % P || W % P)
+  if (B <= 0 || !images || !cls || H <= 0 || W <= 0 || H % d.patch || W % d.patch)
     return fail(enc, MMPFN_ERR_INVALID, "images must be [B][C][H][W] with H, W multiples of the patch size");
   if (precision != PREC_F32 && precision != PREC_BF16) return fail(enc, MMPFN_ERR_INVALID, "bad precision");
-  const int prec = precision;
-  const bool bf = prec == PREC_BF16;
-  const int gh = H / P, gw = W / P, np = gh * gw;
-  const int64_t L = 1 + np, M = (int64_t)B * L;
-  if (M > 0x7fffffffll) return fail(enc, MMPFN_ERR_INVALID, "batch too large");
-  const float eps = d.ln_eps;
-  hipStream_t st = enc->stream;
-  HIPCHK(hipSetDevice(enc->device));
-  RC(ensure_ws(enc, M, B, prec));
-  RC(ensure(enc, enc->P0, (size_t)B * np * D * 4));
-  const float* pe = nullptr;
-  RC(pos_for(enc, gh, gw, &pe));
-  // patch embedding: im2col + GEMM (+ bias) -> [cls | patches] + pos
-  HIPCHK(launch_im2col(images, B, d.in_chans, H, W, P, enc->Kpad, enc->A.p, !bf, st));
-  RC(linear(enc, prec, enc->A.p, enc->pe_w, enc->pe_b, B * np, D, enc->Kpad, GT_F32, 0, enc->P0.p, nullptr, nullptr));
-  float* X = (float*)enc->X.p;
-  HIPCHK(launch_vit_assemble((const float*)enc->P0.p, (const float*)enc->cls_tok.p, pe, B, np, D, X, st));
-  for (int i = 0; i < d.depth; ++i) {
-    const EncLayer& Lw = enc->layers[i];
-    const bool tail = i == d.depth - 1 && tokens == nullptr;
-    // X += ls1 * attn(norm1(X))   (block.py:106-115)
-    HIPCHK(launch_ln_dual(X, M, D, eps, bf ? nullptr : (float*)enc->A.p, bf ? enc->A.p : nullptr,
-                          (const float*)Lw.ln1g.p, (const float*)Lw.ln1b.p, st));
-    RC(linear(enc, prec, enc->A.p, Lw.qkv, Lw.qkv_b, (int)M, 3 * D, D, GT_BF16, 0, enc->QKV.p, nullptr, nullptr));
-    if (tail) {
-      HIPCHK(launch_attn64(enc->QKV.p, nullptr, enc->Oc.p, B, (int)L, nh, 0, 1, 1, prec, st));
-      RC(cls_tail(enc, Lw, B, L, prec, false));
-      break;
-    }
-    HIPCHK(launch_attn64(enc->QKV.p, nullptr, enc->O.p, B, (int)L, nh, 0, (int)L, L, prec, st));
-    RC(linear(enc, prec, enc->O.p, Lw.proj, Lw.proj_b, (int)M, D, D, GT_RESID, 0, X,
-              (const float*)Lw.ls1.p, (float*)enc->Y.p));
-    // X += ls2 * mlp(norm2(X))
-    HIPCHK(launch_ln_dual(X, M, D, eps, bf ? nullptr : (float*)enc->A.p, bf ? enc->A.p : nullptr,
-                          (const float*)Lw.ln2g.p, (const float*)Lw.ln2b.p, st));
-    RC(linear(enc, prec, enc->A.p, Lw.fc1, Lw.fc1_b, (int)M, F, D, GT_BF16, 1, enc->Hh.p, nullptr, nullptr));
-    RC(linear(enc, prec, enc->Hh.p, Lw.fc2, Lw.fc2_b, (int)M, D, F, GT_RESID, 0, X,
-              (const float*)Lw.ls2.p, (float*)enc->Y.p));
-  }
-  // x_norm = norm(x); x_norm_clstoken = x_norm[:, 0]
-  if (tokens) {
-    HIPCHK(launch_ln_dual(X, M, D, eps, tokens, nullptr, (const float*)enc->norm_g.p, (const float*)enc->norm_b.p, st));
-    HIPCHK(launch_gather_rows(tokens, L * D, B, D, cls, 4, st));
-  } else {
-    HIPCHK(launch_ln_dual((const float*)enc->Xc.p, B, D, eps, cls, nullptr, (const float*)enc->norm_g.p,
-                          (const float*)enc->norm_b.p, st));
-  }
+  RC(vit_workspace(enc, B, H, W, precision));
+  HIPCHK(launch_im2col(images, B, d.in_chans, H, W, d.patch, enc->Kpad, enc->A.p, precision != PREC_BF16, enc->stream));
+  return vit_from_patches(enc, B, H, W, cls, tokens, precision);
+}
+
+int mmpfn_resize_coeffs(int in_size, int out_size, int32_t* k, int32_t* bounds, int* ksize) {
+  if (!ksize || in_size <= 0 || out_size <= 0 || in_size > RESIZE_MAX_SIDE || out_size > RESIZE_MAX_SIDE ||
+      (k && !bounds))
+    return MMPFN_ERR_INVALID;
+  *ksize = resize_ksize(in_size, out_size);
+  if (k) resize_coeffs(in_size, out_size, k, bounds);
   return MMPFN_OK;
+}
+
+int mmpfn_pixel_scale_table(float* out) {
+  if (!out) return MMPFN_ERR_INVALID;
+  pixel_scale_table(out);
+  return MMPFN_OK;
+}
+
+int mmpfn_image_patches_rgb(mmpfn_enc* enc, const uint8_t* pixels, const int64_t* offsets, const int32_t* sizes,
+                            int B, int oh, int ow, int patch, int kpad, uint8_t* resized, void* patches,
+                            int precision) {
+  if (!enc) return MMPFN_ERR_INVALID;
+  if (!resized && !patches) return fail(enc, MMPFN_ERR_INVALID, "one of resized and patches is required");
+  if (precision != PREC_F32 && precision != PREC_BF16) return fail(enc, MMPFN_ERR_INVALID, "bad precision");
+  HIPCHK(hipSetDevice(enc->device));
+  return image_front(enc, pixels, offsets, sizes, B, oh, ow, patch, kpad, resized, patches, precision);
+}
+
+int mmpfn_vit_forward_rgb(mmpfn_enc* enc, const uint8_t* pixels, const int64_t* offsets, const int32_t* sizes, int B,
+                          int oh, int ow, float* cls, float* tokens, int precision) {
+  if (!enc) return MMPFN_ERR_INVALID;
+  if (!enc->finalized || enc->d.kind != MMPFN_ENC_VIT) return fail(enc, MMPFN_ERR_STATE, "no finalized ViT model");
+  const auto& d = enc->d;
+  if (d.in_chans != 3) return fail(enc, MMPFN_ERR_INVALID, "the raw-pixel path needs a model with in_chans == 3");
+  if (B <= 0 || !cls || oh <= 0 || ow <= 0 || oh % d.patch || ow % d.patch)
+    return fail(enc, MMPFN_ERR_INVALID, "oh and ow must be positive multiples of the patch size");
+  if (precision != PREC_F32 && precision != PREC_BF16) return fail(enc, MMPFN_ERR_INVALID, "bad precision");
+  RC(vit_workspace(enc, B, oh, ow, precision));
+  RC(image_front(enc, pixels, offsets, sizes, B, oh, ow, d.patch, enc->Kpad, nullptr, enc->A.p, precision));
+  return vit_from_patches(enc, B, oh, ow, cls, tokens, precision);
 }
 
 int mmpfn_enc_attention(mmpfn_enc* enc, const void* qkv, const float* kbias, void* out, int B, int L, int H,

@@ -32,6 +32,22 @@ hipError_t launch_ln_dual(const float* in, int64_t rows, int dim, float eps, flo
 
 hipError_t launch_im2col(const float* img, int B, int C, int H, int W, int P, int Kpad, void* out, bool out_f32,
                          hipStream_t st);
+// Image front end (imgprep.hip): a ragged batch of RGB uint8 images -> Pillow's bilinear resize to oh x ow ->
+// the im2col rows launch_im2col writes from the resized image / 255 (patches, fp32 or bf16, 16-B aligned, may be
+// null) and / or the resized uint8 [B][oh][ow][3] image (may be null).  desc [B] and tab are device memory; the
+// k* / *b fields index tab (int32 units): k [out][ksize] and bounds [out][2] of img_coeffs.h per axis.  lut: the
+// 256 values of pixel_scale_table.  max_w: the widest image of the batch (sizes the LDS row stage); max_ksh: its
+// longest row of horizontal taps (kept in LDS when short enough).
+constexpr int IMGPREP_PMAX = 16;  // largest patch: the band's accumulators live in registers
+struct ImgPrepDesc {
+  int64_t pix_off;  // byte offset of the image's first pixel
+  int32_t H, W;
+  int32_t kh, hb, ksh;  // horizontal table (W -> ow)
+  int32_t kv, vb, ksv;  // vertical table (H -> oh)
+};
+hipError_t launch_imgprep(const uint8_t* pixels, const ImgPrepDesc* desc, const int32_t* tab, const float* lut, int B,
+                          int max_w, int max_ksh, int oh, int ow, int P, int Kpad, uint8_t* resized, void* patches,
+                          bool out_f32, hipStream_t st);
 // bicubic resampling of a [1 + M*M][D] positional table to [1 + oh*ow][D]; sh / sw = source pixels
 // per output pixel (torch upsample_bicubic2d with the given scale factors)
 hipError_t launch_pos_interp(const float* pos, int M, int D, int oh, int ow, float sh, float sw, float* out,

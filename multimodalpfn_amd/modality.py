@@ -21,6 +21,12 @@ vocabulary are not available offline: parity is pinned with seeded random weight
 reference's own ``vit_base`` and transformers' ``ElectraModel`` (``tests/golden/make_modality_golden.py``),
 and the text tower takes token ids (``input_ids`` / ``attention_mask`` / ``token_type_ids``, what the
 reference's tokenizer returns).
+
+The image tower also starts from the decoded pictures themselves (``cls_embeddings_from_pixels``,
+``embed_raw_images``): RGB uint8 arrays of any sizes are packed, uploaded once, and resized on the device exactly as
+the reference's ``img.resize((img_size, img_size), Image.BILINEAR)`` followed by ``/ 255.0`` does
+(``pad_ufes_20.py:53-61``, ``cbis_ddsm.py:71-81``, ``petfinder.py:85-95``) -- bit for bit, so both paths give the
+same embeddings.
 """
 
 from __future__ import annotations
@@ -41,6 +47,7 @@ __all__ = [
     "ElectraConfigLite",
     "ElectraTextEncoder",
     "embed_images",
+    "embed_raw_images",
     "embed_texts",
 ]
 
@@ -272,6 +279,68 @@ class DinoVisionTransformer(_DeviceTower):
         """``forward_features(x)["x_norm_clstoken"]`` only: the last block runs on the CLS rows alone."""
         return self._run(x, want_tokens=False)[0]
 
+    # ---- from raw pixels: the reference's Pillow resize + / 255 runs on the device (csrc/imgprep.hip)
+    def _pack_pixels(self, images, device: torch.device):
+        """``images`` (uint8 [H, W, 3] arrays / tensors of any sizes) -> (device bytes, int64 offsets, int32 sizes):
+        one pinned staging buffer and one upload (device tensors are concatenated where they are)."""
+        ts = []
+        for i, im in enumerate(images):
+            t = im if isinstance(im, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(im))
+            if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3:
+                raise ValueError(f"image {i}: expected uint8 [H, W, 3], got {t.dtype} {tuple(t.shape)}")
+            if t.numel() == 0:
+                raise ValueError(f"image {i} is empty ({t.shape[0]} x {t.shape[1]})")
+            ts.append(t)
+        if not ts:
+            raise ValueError("no images")
+        sizes = np.array([[t.shape[0], t.shape[1]] for t in ts], np.int32)
+        lens = np.array([t.numel() for t in ts], np.int64)
+        offsets = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+        if all(t.device.type == "cuda" for t in ts):
+            return torch.cat([t.to(device).reshape(-1) for t in ts]), offsets, sizes
+        stage = torch.empty(int(lens.sum()), dtype=torch.uint8, pin_memory=True)
+        for t, o, n in zip(ts, offsets, lens):
+            stage[int(o):int(o + n)].copy_(t.reshape(-1))
+        return stage.to(device, non_blocking=True), offsets, sizes
+
+    def _run_pixels(self, images, img_size, want_tokens: bool):
+        oh, ow = (img_size, img_size) if isinstance(img_size, int) else img_size
+        if oh <= 0 or ow <= 0 or oh % self.patch_size or ow % self.patch_size:
+            raise ValueError(f"img_size ({oh}, {ow}) must be a positive multiple of the patch size {self.patch_size}")
+        images = list(images)
+        dev = next((t.device for t in images if isinstance(t, torch.Tensor) and t.device.type == "cuda"), None)
+        ctx = self.context(dev)
+        prec = _precision(self.precision, ctx.device)
+        with torch.cuda.device(ctx.device):
+            buf, offsets, sizes = self._pack_pixels(images, ctx.device)
+            B = len(images)
+            cls = torch.empty((B, self.embed_dim), device=ctx.device, dtype=torch.float32)
+            L = 1 + (oh // self.patch_size) * (ow // self.patch_size)
+            tok = torch.empty((B, L, self.embed_dim), device=ctx.device, dtype=torch.float32) if want_tokens else None
+            ctx.bind()
+            ctx._check(ctx.lib.mmpfn_vit_forward_rgb(ctx.enc, buf.data_ptr(), offsets.ctypes.data_as(ctypes.c_void_p),
+                                                     sizes.ctypes.data_as(ctypes.c_void_p), B, oh, ow, cls.data_ptr(),
+                                                     None if tok is None else tok.data_ptr(), prec),
+                       "mmpfn_vit_forward_rgb")
+        return cls, tok
+
+    def forward_features_from_pixels(self, images, img_size=14 * 24):
+        """``forward_features`` of the pictures as decoded: ``images`` is a sequence of RGB uint8 ``[H, W, 3]`` arrays
+        or tensors of any sizes, each resized to ``img_size`` (an int or ``(height, width)``) as the reference's
+        ``img.resize(..., Image.BILINEAR)`` does, then scaled by 1 / 255."""
+        cls, tok = self._run_pixels(images, img_size, want_tokens=True)
+        return {
+            "x_norm_clstoken": cls,
+            "x_norm_regtokens": tok[:, 1:1],
+            "x_norm_patchtokens": tok[:, 1:],
+            "x_prenorm": None,
+            "masks": None,
+        }
+
+    def cls_embeddings_from_pixels(self, images, img_size=14 * 24) -> torch.Tensor:
+        """``forward_features_from_pixels(images, img_size)["x_norm_clstoken"]`` only."""
+        return self._run_pixels(images, img_size, want_tokens=False)[0]
+
     def forward(self, *args, is_training=False, **kwargs):
         """``forward`` (vision_transformer.py:329-334): the head (Identity) of the CLS token."""
         if is_training:
@@ -470,6 +539,22 @@ def embed_images(encoder: DinoVisionTransformer, images, batch_size: int = 16) -
         embs = encoder.cls_embeddings(flat.to("cuda", non_blocking=True))
         out.append(embs.reshape(-1, n_img, embs.shape[-1]).cpu())
     return torch.cat(out, 0)
+
+
+def embed_raw_images(encoder: DinoVisionTransformer, images, img_size=14 * 24, batch_size: int = 128) -> torch.Tensor:
+    """``embed_images`` from the pictures as decoded: ``images[i][j]`` = image j of row i, RGB uint8 ``[H, W, 3]`` of
+    any size.  The reference's ``get_images`` resize (pad_ufes_20.py:53-61, cbis_ddsm.py:71-81, petfinder.py:85-95)
+    runs on the device; rows go in batches of ``batch_size`` -> ``[N, n_img, D]`` CLS embeddings on the host."""
+    rows = [list(r) for r in images]
+    n_img = len(rows[0]) if rows else 0
+    if any(len(r) != n_img for r in rows):
+        raise ValueError("every row must hold the same number of images")
+    out = []
+    for i in range(0, len(rows), batch_size):
+        flat = [im for r in rows[i:i + batch_size] for im in r]
+        embs = encoder.cls_embeddings_from_pixels(flat, img_size)
+        out.append(embs.reshape(-1, n_img, embs.shape[-1]).cpu())
+    return torch.cat(out, 0) if out else torch.empty((0, n_img, encoder.embed_dim))
 
 
 def embed_texts(encoder: ElectraTextEncoder, token_ids, batch_size: int = 64) -> torch.Tensor:
