@@ -34,6 +34,10 @@
  *   mmpfn_bar_score / mmpfn_bar_head_score
  *       <- model/bar_distribution.py:487-571 forward (the negative log density), :59-97 cdf, :629-675 pi,
  *          :677-758 ei, :600-626 mean_of_square of FullSupportBarDistribution; alone, or fused into mmpfn_bar_head
+ *   mmpfn_bar_sample
+ *       <- model/bar_distribution.py:577-585 sample (one uniform level per draw, then :256-283 icdf), many draws
+ *          per row; the levels from Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel Random Numbers: As Easy
+ *          as 1, 2, 3", SC'11) where the reference calls torch.rand
  *   mmpfn_status
  *       <- model/transformer.py:727-731,790-796 NaN checks (ValueError)
  *   mmpfn_feature_attention / mmpfn_item_attention_block / mmpfn_mlp_ln
@@ -228,6 +232,31 @@ int mmpfn_bar_head_score(mmpfn_ctx* ctx, const float* logits, int M, int Q, int 
                          const float* levels, int K, float* out_logits, float* mean, float* mode, float* quantiles,
                          const float* log_widths, const float* mean_squares, const float* ei_mids, const float* ends,
                          const float* ys, int J, float* nll, float* cdf, float* pi, float* ei, float* mean_of_square);
+
+/* Draws from bar distributions (FullSupportBarDistribution.sample, bar_distribution.py:577-585, with many levels per
+ * row), always fp32, blocks of MMPFN_BAR_SAMPLE_CHUNK draws of one row:
+ * logits [Q][B], softmax(logits * inv_temperature) as mmpfn_bar_score computes it (inv_temperature = 1 / t of the
+ *   reference's sample(logits, t)); borders [B + 1]; ends [MMPFN_BAR_SCORE_ENDS] as mmpfn_bar_score's (NULL is fine
+ *   with tails 0);
+ * n draws per row, 0 <= n <= MMPFN_BAR_MAX_DRAWS, out [Q][n]; draw j of the call is draw J = first_draw + j of the row.
+ * Its level u: uniforms[q][j] clamped into [2^-24, 1 - 2^-24] (a NaN level gives a NaN draw), or with uniforms NULL
+ *   word J & 3 (Random123's output order) of Philox4x32-10 at counter (lo32(J >> 2), hi32(J >> 2), q, 0) and key
+ *   (lo32(seed), hi32(seed)), mapped to u = (2 (x >> 9) + 1) 2^-24: a draw depends on (seed, q, J) alone, not on n or
+ *   on how a row's draws are split over calls.  u_out [Q][n] (NULL: not stored) receives the levels used.
+ * The draw, tails 0: lv = min(u, the row's rounded total); j the first bar whose inclusive cumulative sum reaches lv
+ *   (:256-283); share = clamp((lv - sum before j) / p_j, 0, 1); y = borders[j] + (borders[j + 1] - borders[j]) share.
+ *   The min and the clamp are this engine's own: every draw is finite and inside [borders[0], borders[B]].
+ * tails 1: the two end buckets follow the half-normals that forward / pi / ei give them (:487-571), the draws the
+ *   density mmpfn_bar_score's nll scores: in the last bucket y = borders[B - 1] + ends[1] sqrt(2) erfinv(min(share,
+ *   1 - 2^-24)), in the first y = borders[1] - ends[0] sqrt(2) erfinv(min(1 - share, 1 - 2^-24)).
+ * A row whose total is 0 or NaN (no finite largest logit) gives NaN draws and nothing else.
+ * MMPFN_ERR_INVALID: B (2 .. MMPFN_BAR_MAX_BARS) or n out of range, inv_temperature <= 0, tails not 0 / 1 (or 1 with
+ * ends NULL), out NULL with n > 0.  Q = 0 or n = 0 launch nothing. */
+#define MMPFN_BAR_SAMPLE_CHUNK 4096
+#define MMPFN_BAR_MAX_DRAWS (65535LL * MMPFN_BAR_SAMPLE_CHUNK)
+int mmpfn_bar_sample(mmpfn_ctx* ctx, const float* logits, int Q, int B, float inv_temperature, const float* borders,
+                     const float* ends, int tails, const float* uniforms, uint64_t seed, uint64_t first_draw, int64_t n,
+                     float* out, float* u_out);
 
 /* Synchronises the context stream and reports deferred device-side errors
  * (MMPFN_ERR_NAN when the embedded input held NaNs). */

@@ -1170,6 +1170,28 @@ int mmpfn_bar_head_score(mmpfn_ctx* ctx, const float* logits, int M, int Q, int 
   return MMPFN_OK;
 }
 
+static_assert(MMPFN_BAR_SAMPLE_CHUNK == kBarSampleChunk && MMPFN_BAR_MAX_DRAWS == kBarSampleMaxDraws,
+              "the header's sampling limits are the kernel's");
+
+int mmpfn_bar_sample(mmpfn_ctx* ctx, const float* logits, int Q, int B, float inv_temperature, const float* borders,
+                     const float* ends, int tails, const float* uniforms, uint64_t seed, uint64_t first_draw, int64_t n,
+                     float* out, float* u_out) {
+  if (!ctx) return MMPFN_ERR_INVALID;
+  if (!logits || !borders || Q < 0 || !(inv_temperature > 0.f))
+    return fail(ctx, MMPFN_ERR_INVALID, "mmpfn_bar_sample: null argument, negative size or temperature <= 0");
+  if (B < 2 || B > MMPFN_BAR_MAX_BARS) return fail(ctx, MMPFN_ERR_INVALID, "mmpfn_bar_sample: B outside 2 .. MMPFN_BAR_MAX_BARS");
+  if (n < 0 || n > MMPFN_BAR_MAX_DRAWS)
+    return fail(ctx, MMPFN_ERR_INVALID, "mmpfn_bar_sample: n outside 0 .. MMPFN_BAR_MAX_DRAWS");
+  if ((tails != 0 && tails != 1) || (tails == 1 && !ends))
+    return fail(ctx, MMPFN_ERR_INVALID, "mmpfn_bar_sample: tails outside 0 / 1, or half-normal tails without ends");
+  if (n > 0 && !out) return fail(ctx, MMPFN_ERR_INVALID, "mmpfn_bar_sample: draws without an output");
+  if (Q == 0 || n == 0) return MMPFN_OK;
+  HIPCHK(hipSetDevice(ctx->device));
+  const BarSampleArgs a{logits, borders, ends, uniforms, out, u_out, seed, first_draw, n, B, tails, inv_temperature};
+  HIPCHK(launch_bar_sample(a, Q, ctx->stream));
+  return MMPFN_OK;
+}
+
 int mmpfn_status(mmpfn_ctx* ctx) {
   if (!ctx) return MMPFN_ERR_INVALID;
   HIPCHK(hipSetDevice(ctx->device));

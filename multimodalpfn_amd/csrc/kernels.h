@@ -305,6 +305,26 @@ struct BarScoreArgs {
 hipError_t launch_bar_score(const float* logits /*[Q][B]*/, int Q, int B, float inv_temp, const BarScoreArgs& score,
                             hipStream_t st);
 
+// Draws from the rows' distributions (barsample.hip bar_sample_kernel): n draws per row of softmax(logits * inv_temp),
+// blocks of kBarSampleChunk draws (grid Q x chunks).  Draw J = first_draw + j of row q reads the level uniforms[q][j],
+// or without uniforms the Philox4x32-10 word of (seed, q, J); tails 1: the two end buckets follow their half-normals
+// (ends [kBarScoreEnds], may be null with tails 0).  out [Q][n]; u_out [Q][n] the levels used, or null.
+constexpr int kBarSampleChunk = 4096;
+constexpr int64_t kBarSampleMaxDraws = (int64_t)65535 * kBarSampleChunk;
+struct BarSampleArgs {
+  const float* logits;    // [Q][B]
+  const float* borders;   // [B + 1]
+  const float* ends;      // [kBarScoreEnds] or null (tails 0)
+  const float* uniforms;  // [Q][n] or null
+  float* out;             // [Q][n]
+  float* u_out;           // [Q][n] or null
+  uint64_t seed, first_draw;
+  int64_t n;
+  int B, tails;
+  float inv_temp;
+};
+hipError_t launch_bar_sample(const BarSampleArgs& a, int Q, hipStream_t st);
+
 // ---- mixer helpers -----------------------------------------------------------------
 hipError_t launch_layernorm_rows(const float* in, int64_t rows, int dim, float eps, void* out, DType out_t,
                                  const float* gamma, const float* beta, hipStream_t st);

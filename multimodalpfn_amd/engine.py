@@ -540,6 +540,49 @@ class HipEngine:
         )
         return out
 
+    SAMPLE_TAILS = {"linear": 0, "halfnormal": 1}  # mmpfn_bar_sample's tails
+
+    def bar_sample(self, logits: torch.Tensor, criterion_tables: dict, n: int, *, seed: int = 0, first_draw: int = 0,
+                   uniforms=None, temperature: float = 1.0, tails: str = "linear", return_uniforms: bool = False):
+        """``n`` draws per row from the bar distributions ``softmax(logits / temperature)`` ``[Q, B]`` on the device
+        (``mmpfn_bar_sample``): a device tensor ``[Q, n]``, with ``return_uniforms`` also the levels used ``[Q, n]``.
+        ``criterion_tables`` as ``bar_score`` takes them (``borders``, and ``ends`` for the half-normal tails).
+        Draw ``j`` of the call is draw ``first_draw + j`` of its row and depends on ``(seed, row, first_draw + j)``
+        alone, so a row's draws may be split over calls; ``uniforms`` ``[Q, n]`` supplies the levels instead.
+        ``tails``: ``"linear"`` (the reference's ``sample``) or ``"halfnormal"`` (the end buckets as the density
+        ``bar_score``'s ``nll`` scores has them)."""
+        lg = logits.to(self.device, torch.float32).contiguous()
+        Q, B = lg.shape
+        n = int(n)
+        if not 2 <= B <= _lib.BAR_MAX_BARS:
+            raise ValueError(f"mmpfn_bar_sample holds 2..{_lib.BAR_MAX_BARS} bars; got {B}")
+        if not 0 <= n <= _lib.BAR_MAX_DRAWS:
+            raise ValueError(f"mmpfn_bar_sample holds 0..{_lib.BAR_MAX_DRAWS} draws per row; got {n}")
+        if not temperature > 0:
+            raise ValueError(f"temperature must be > 0, got {temperature}")
+        if tails not in self.SAMPLE_TAILS:
+            raise ValueError(f"tails must be one of {sorted(self.SAMPLE_TAILS)}, got {tails!r}")
+        if not (0 <= int(seed) < 2 ** 64 and 0 <= int(first_draw) < 2 ** 64):
+            raise ValueError("seed and first_draw are unsigned 64-bit numbers")
+        t = self._score_tables(criterion_tables, B, ("borders", "ends") if tails == "halfnormal" else ("borders",))
+        ud = None
+        if uniforms is not None:
+            ud = self._dev(uniforms).contiguous()
+            if tuple(ud.shape) != (Q, n):
+                raise ValueError(f"uniforms [{Q}, {n}] expected, got {tuple(ud.shape)}")
+        out = torch.empty((Q, n), device=self.device, dtype=torch.float32)
+        u_out = torch.empty((Q, n), device=self.device, dtype=torch.float32) if return_uniforms else None
+        if Q == 0 or n == 0:  # nothing to launch, and an empty tensor has no address to pass
+            return (out, u_out) if return_uniforms else out
+        self._bind_stream()
+        self._check(
+            self.lib.mmpfn_bar_sample(self.ctx, _ptr(lg), Q, B, 1.0 / float(temperature), _ptr(t["borders"]),
+                                      _ptr(t.get("ends")), self.SAMPLE_TAILS[tails], _ptr(ud), int(seed),
+                                      int(first_draw), n, _ptr(out), _ptr(u_out)),
+            "mmpfn_bar_sample",
+        )
+        return (out, u_out) if return_uniforms else out
+
     def bar_head(self, logits: torch.Tensor, idx, share, criterion: dict, *, cancel=None,
                  softmax_temperature: float = 1.0, average_before_softmax: bool = False, quantiles=(),
                  want_logits: bool = False, targets=None, score_tables: dict | None = None) -> dict:

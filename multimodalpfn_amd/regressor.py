@@ -9,7 +9,8 @@ Every forward runs in ``libmmpfn_hip.so`` on an MI355X, and so does the whole po
 borders, the ensemble mean, and the criterion's mean / median / mode / quantiles -- in one kernel over the
 members' logits where they lie (``mmpfn_bar_head``); only what the ``output_type`` asks for is copied back.
 ``score_samples`` (log predictive density) and ``acquisition`` (``ei`` / ``pi`` / ``ucb``) score the rows in that same
-kernel (``mmpfn_bar_head_score``).
+kernel (``mmpfn_bar_head_score``); ``sample`` / ``sample_device`` draw from each row's distribution on the device
+(``mmpfn_bar_sample``).
 There is no CPU forward: without a ROCm GPU ``fit`` / ``predict`` raise the engine's ``RuntimeError``.
 """
 
@@ -296,6 +297,29 @@ class MMPFNRegressor(RegressorMixin, BaseEstimator):
         n_rows = len(X) if X is not None else len(image_test)
         best = np.array(np.broadcast_to(np.asarray(best_f, dtype=np.float32), (n_rows,)))
         return self.predict_device(X, image_test, targets=best)[kind][:, 0].cpu().numpy()
+
+    def sample_device(self, X, image_test: np.ndarray | None, n_samples: int = 1, *, random_state=None,
+                      uniforms=None, temperature: float = 1.0,
+                      tails: Literal["linear", "halfnormal"] = "linear") -> torch.Tensor:
+        """``n_samples`` draws from each row's predictive distribution on the target's original scale, a device
+        tensor ``[Q, n_samples]`` (``HipEngine.bar_sample`` on the head's log-probabilities where they lie: nothing
+        of the bars' size reaches the host).  ``random_state`` (``None``, an int or a ``np.random.Generator``) gives
+        the one 64-bit seed of the device generator, so equal ints give equal draws; ``uniforms`` ``[Q, n_samples]``
+        supplies the levels instead.  ``temperature`` is the ``t`` of the reference's ``sample(logits, t)``, on top
+        of ``softmax_temperature``, which the head has applied.  ``tails``: ``"linear"`` as the reference's ``sample``,
+        or ``"halfnormal"``, the end buckets as ``score_samples`` scores them."""
+        seed = int(np.random.default_rng(random_state).integers(0, 2 ** 64, dtype=np.uint64))
+        logits = self.predict_device(X, image_test, want_logits=True)["logits"]
+        eng = self.model_.engine(logits.device)
+        crit = self.renormalized_criterion_
+        return eng.bar_sample(logits, {**crit.head_tables(), **crit.score_tables()}, n_samples, seed=seed,
+                              uniforms=uniforms, temperature=temperature, tails=tails)
+
+    def sample(self, X, image_test: np.ndarray | None, n_samples: int = 1, *, random_state=None, uniforms=None,
+               temperature: float = 1.0, tails: Literal["linear", "halfnormal"] = "linear") -> np.ndarray:
+        """``sample_device`` as float32 numpy ``[Q, n_samples]``."""
+        return self.sample_device(X, image_test, n_samples, random_state=random_state, uniforms=uniforms,
+                                  temperature=temperature, tails=tails).cpu().numpy()
 
     def predict(self, X, image_test: np.ndarray | None, *,
                 output_type: Literal["mean", "median", "mode", "quantiles", "full", "main"] = "mean",
