@@ -38,6 +38,9 @@
  *       <- model/bar_distribution.py:577-585 sample (one uniform level per draw, then :256-283 icdf), many draws
  *          per row; the levels from Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel Random Numbers: As Easy
  *          as 1, 2, 3", SC'11) where the reference calls torch.rand
+ *   mmpfn_xform_create / mmpfn_xform_free / mmpfn_member_transform
+ *       <- model/preprocessing.py:443-1200 (the members' fitted steps, test form) as preprocessing.py:416-473 chains
+ *          them, called per member at inference.py:294-349
  *   mmpfn_status
  *       <- model/transformer.py:727-731,790-796 NaN checks (ValueError)
  *   mmpfn_feature_attention / mmpfn_item_attention_block / mmpfn_mlp_ln
@@ -258,8 +261,36 @@ int mmpfn_bar_sample(mmpfn_ctx* ctx, const float* logits, int Q, int B, float in
                      const float* ends, int tails, const float* uniforms, uint64_t seed, uint64_t first_draw, int64_t n,
                      float* out, float* u_out);
 
+/* Member preprocessing of the test rows on the device.  Replaces, per member and predict, the host's
+ * preprocessor.transform(X).X of inference.py:294-349: the fitted steps of model/preprocessing.py (constant removal
+ * :443-473, the distribution reshape with its ColumnTransformer, uniform QuantileTransformer, guarded scalers and
+ * TruncatedSVD :579-995, the ordinal re-encoding :998-1200, the fingerprint :476-523, the column shuffle :526-571) as
+ * preprocessing.py:416-473 chains them, with the estimator's ordinal front encoder (classifier.py:529-532) in front.
+ * A program is what multimodalpfn_amd/device_transform.py compiles from the fitted state and documents:
+ *   ops [n_ops][8] int32 (code, width in, width out, int offset, double offset, a, b, c), codes 1 gather, 2 map
+ *   (five ints per column: source, kind 0 pass / 1 lookup / 2 uniform quantile / 3 guarded scale, double offset, n,
+ *   aux), 3 svd, 4 fingerprint; ints and doubles are the parameter blobs the offsets point into.
+ * The create call copies the three arrays (HOST pointers) to the device after checking every width, offset and index
+ * in them: MMPFN_ERR_INVALID (mmpfn_last_error says why) for an op or map kind out of range, widths that do not chain,
+ * a row wider than MMPFN_XFORM_MAX_WIDTH doubles (two working rows of that width are the 64 KiB of LDS a block
+ * holds), or anything that points outside a blob or a row.  The program belongs to the context; free it with
+ * the free call below (which waits for the context's streams).
+ * The transform call runs a program over rows [0, Q) of x (device, row-major [Q][ldx], float32 or float64 by
+ * x_is_f64) on the bound stream, one launch, all arithmetic in float64, and writes out32 [Q][ld32] (float32, round
+ * to nearest even) and, if not NULL, out64 [Q][ld64] (the float64 values before that rounding).  F_in must be the
+ * program's input width, ldx >= F_in, ld32 / ld64 >= the program's output width, else MMPFN_ERR_INVALID.  NaN cells
+ * are data (as on the host); a +-inf cell sets a flag that mmpfn_status reports as MMPFN_ERR_NAN with the host
+ * path's message ("Input X contains infinity ...").  Q = 0 launches nothing. */
+#define MMPFN_XFORM_MAX_WIDTH 4096
+typedef struct mmpfn_xform mmpfn_xform;
+int mmpfn_xform_create(mmpfn_ctx* ctx, const int32_t* ops, int n_ops, const int32_t* ints, int64_t n_ints,
+                       const double* doubles, int64_t n_doubles, int n_in, mmpfn_xform** out);
+void mmpfn_xform_free(mmpfn_ctx* ctx, mmpfn_xform* prog);
+int mmpfn_member_transform(mmpfn_ctx* ctx, const mmpfn_xform* prog, const void* x, int x_is_f64, int Q, int F_in,
+                           int64_t ldx, float* out32, int64_t ld32, double* out64, int64_t ld64);
+
 /* Synchronises the context stream and reports deferred device-side errors
- * (MMPFN_ERR_NAN when the embedded input held NaNs). */
+ * (MMPFN_ERR_NAN when the embedded input held NaNs, or a device X held an infinity). */
 int mmpfn_status(mmpfn_ctx* ctx);
 
 /* ---- raw kernels (benchmarks / unit parity) ------------------------------------

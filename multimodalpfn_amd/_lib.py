@@ -24,6 +24,7 @@ BAR_MAX_BARS, BAR_MAX_MEMBERS, BAR_MAX_LEVELS = 8192, 1024, 64  # mmpfn_bar_head
 BAR_MAX_TARGETS, BAR_SCORE_ENDS = 64, 9  # mmpfn_bar_score's (MMPFN_BAR_MAX_TARGETS, MMPFN_BAR_SCORE_ENDS)
 BAR_SAMPLE_CHUNK = 4096  # draws of one row per block of mmpfn_bar_sample (MMPFN_BAR_SAMPLE_CHUNK)
 BAR_MAX_DRAWS = 65535 * BAR_SAMPLE_CHUNK  # draws per row in one call (MMPFN_BAR_MAX_DRAWS)
+XFORM_MAX_WIDTH = 4096  # doubles of a member program's widest row (MMPFN_XFORM_MAX_WIDTH)
 
 PREC_F32 = 0       # parity mode: split-bf16 three-product MFMAs (fp32 operands to 2^-16), fp32 softmax / LN
 PREC_BF16 = 1      # 16-bit mode with bf16 operands on an fp32 state (MMPFN_AUTOCAST=bf16)
@@ -143,6 +144,9 @@ SIGNATURES = [
     ("mmpfn_bar_head_score", _i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp,
                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     ("mmpfn_bar_sample", _i, [_vp, _vp, _i, _i, _f, _vp, _vp, _i, _vp, _u64, _u64, _i64, _vp, _vp]),
+    ("mmpfn_xform_create", _i, [_vp, _vp, _i, _vp, _i64, _vp, _i64, _i, ctypes.POINTER(_vp)]),
+    ("mmpfn_xform_free", None, [_vp, _vp]),
+    ("mmpfn_member_transform", _i, [_vp, _vp, _vp, _i, _i, _i, _i64, _vp, _i64, _vp, _i64]),
 ]
 
 # include/mmpfn_modality.h (modality encoders: DINOv2 ViT, ELECTRA text tower)

@@ -29,6 +29,7 @@ from multimodalpfn_amd.constants import (
     SKLEARN_16_DECIMAL_PRECISION,
     ModelInterfaceConfig,
 )
+from multimodalpfn_amd.device_transform import device_table
 from multimodalpfn_amd.preprocessing import EnsembleConfig, default_classifier_preprocessor_configs
 from multimodalpfn_amd.utils import (
     _fix_dtypes,
@@ -199,6 +200,8 @@ class MMPFNClassifier(ClassifierMixin, BaseEstimator):
             memory_saving_mode=self.memory_saving_mode,
             use_autocast_=self.use_autocast_,
         )
+        if X is not None:  # the members' device programs take the raw table: the front encoder's plan goes first
+            self.executor_.attach_front(self._ordinal_plan_)
         return self
 
     # ------------------------------------------------------------------ predict
@@ -275,7 +278,10 @@ class MMPFNClassifier(ClassifierMixin, BaseEstimator):
         self._ordinal_plan_ = (cols, cats, miss, lut, rem)
 
     def predict(self, X, X_image: np.ndarray | None) -> np.ndarray:
-        """Arg-max class labels (``classifier.py:504-515``)."""
+        """Arg-max class labels (``classifier.py:504-515``).  ``X`` here and in ``predict_proba`` /
+        ``predict_proba_device``: an array or DataFrame, or a CUDA tensor ``[Q, n_features_in_]`` on the estimator's
+        device, which is encoded and preprocessed there (``device_transform.py``; members whose pipeline has a step
+        without a device form, and ``fit_mode="low_memory"``, transform its host copy)."""
         proba = self.predict_proba(X, X_image)
         return self.label_encoder_.inverse_transform(np.argmax(proba, axis=1))
 
@@ -287,7 +293,9 @@ class MMPFNClassifier(ClassifierMixin, BaseEstimator):
             if image_test is not None:
                 # the mixer first: it does not need X, so the host's validation / encoding of X runs under it
                 ex.launch_mixer_early(image_test, device=self.device_, autocast=self.use_autocast_)
-            if X is not None:
+            if isinstance(X, torch.Tensor) and X.is_cuda:
+                X = device_table(self, X, self.device_, self._encode_predict_X)
+            elif X is not None:
                 X = self._encode_predict_X(X)
             logits, perms = [], []
             ex._defer_status = True  # the NaN / error check runs after the aggregation is enqueued (below)

@@ -77,6 +77,12 @@ struct mmpfn_cache {
   DevBuf pe;     // positional embeddings [G + C][E]
 };
 
+// a member's compiled preprocessing program (device_transform.py) on the device, checked when it was made
+struct mmpfn_xform {
+  DevBuf ops, ints, dbl;
+  int n_ops = 0, n_in = 0, n_out = 0, width = 0;
+};
+
 struct mmpfn_ctx : Lane {  // the Lane base is the selected lane
   int device = 0;
   hipStream_t stream = nullptr;
@@ -1192,6 +1198,117 @@ int mmpfn_bar_sample(mmpfn_ctx* ctx, const float* logits, int Q, int B, float in
   return MMPFN_OK;
 }
 
+// Why a program cannot be run (null: it can), and its output width and widest row.  Every index the kernel forms is
+// checked here, against the host copies of the blobs, so the kernel itself never indexes past its buffers.
+static const char* xform_refusal(const int32_t* ops, int n_ops, const int32_t* ints, int64_t n_ints, int64_t n_dbl,
+                                 int n_in, int& n_out, int& widest) {
+  if (n_ops < 0 || n_ints < 0 || n_dbl < 0 || (n_ops > 0 && !ops) || (n_ints > 0 && !ints)) return "null blob or negative size";
+  if (n_in < 1 || n_in > kXformMaxWidth) return "input width outside 1 .. MMPFN_XFORM_MAX_WIDTH";
+  int w = n_in;
+  widest = n_in;
+  for (int k = 0; k < n_ops; ++k) {
+    const int32_t* op = ops + (int64_t)k * kXformOpInts;
+    const int code = op[0], w_in = op[1], w_out = op[2];
+    const int64_t ioff = op[3], doff = op[4];
+    if (w_in != w) return "an op's input width is not its predecessor's output width";
+    if (w_out < 1 || w_out > kXformMaxWidth) return "an op's output width outside 1 .. MMPFN_XFORM_MAX_WIDTH";
+    if (ioff < 0 || ioff > n_ints || doff < 0 || doff > n_dbl) return "an op's blob offset out of range";
+    if (code == kXformGather) {
+      if (ioff + w_out > n_ints) return "gather indices past the int blob";
+      for (int j = 0; j < w_out; ++j)
+        if (ints[ioff + j] < 0 || ints[ioff + j] >= w_in) return "gather index outside the input row";
+    } else if (code == kXformMap) {
+      if (ioff + (int64_t)kXformMapInts * w_out > n_ints) return "map columns past the int blob";
+      for (int j = 0; j < w_out; ++j) {
+        const int32_t* c = ints + ioff + (int64_t)j * kXformMapInts;
+        const int64_t off = c[2], n = c[3], aux = c[4];
+        if (c[0] < 0 || c[0] >= w_in) return "map source outside the input row";
+        if (c[1] == kXformPass) continue;
+        if (off < 0 || n < 0) return "map parameters at a negative offset or count";
+        if (c[1] == kXformLookup) {
+          if (off + 2 + 2 * n > n_dbl) return "lookup table past the double blob";
+        } else if (c[1] == kXformQuantile) {
+          if (n < 1 || off + n > n_dbl || aux < 0 || aux + n > n_dbl) return "quantiles past the double blob";
+        } else if (c[1] == kXformScale) {
+          if (off + 4 > n_dbl) return "scaler parameters past the double blob";
+        } else {
+          return "map kind out of range";
+        }
+      }
+    } else if (code == kXformSvd) {
+      const int64_t a = op[5], b = op[6], c = op[7];
+      if (a < 0 || b < 1 || c < 1 || a + b != w_in || a + c != w_out) return "svd widths do not fit the op";
+      if (doff + b * c > n_dbl) return "svd components past the double blob";
+    } else if (code == kXformFingerprint) {
+      if (w_out != w_in + 1 || doff + 1 > n_dbl) return "fingerprint width or salt out of range";
+    } else {
+      return "op code out of range";
+    }
+    w = w_out;
+    if (w > widest) widest = w;
+  }
+  n_out = w;
+  return nullptr;
+}
+
+int mmpfn_xform_create(mmpfn_ctx* ctx, const int32_t* ops, int n_ops, const int32_t* ints, int64_t n_ints,
+                       const double* doubles, int64_t n_doubles, int n_in, mmpfn_xform** out) {
+  if (!ctx || !out) return MMPFN_ERR_INVALID;
+  *out = nullptr;
+  if (n_doubles > 0 && !doubles) return fail(ctx, MMPFN_ERR_INVALID, "mmpfn_xform_create: null double blob");
+  int n_out = 0, widest = 0;
+  if (const char* why = xform_refusal(ops, n_ops, ints, n_ints, n_doubles, n_in, n_out, widest))
+    return fail(ctx, MMPFN_ERR_INVALID, std::string("mmpfn_xform_create: ") + why);
+  HIPCHK(hipSetDevice(ctx->device));
+  mmpfn_xform* p = new mmpfn_xform;
+  p->n_ops = n_ops, p->n_in = n_in, p->n_out = n_out, p->width = widest;
+  const std::pair<DevBuf*, std::pair<const void*, size_t>> parts[] = {
+      {&p->ops, {ops, (size_t)n_ops * kXformOpInts * 4}}, {&p->ints, {ints, (size_t)n_ints * 4}},
+      {&p->dbl, {doubles, (size_t)n_doubles * 8}}};
+  for (const auto& [buf, src] : parts) {
+    int rc = ensure(ctx, *buf, src.second ? src.second : 8);  // an empty blob still gets an address
+    if (rc == MMPFN_OK && src.second && hipMemcpy(buf->p, src.first, src.second, hipMemcpyHostToDevice) != hipSuccess)
+      rc = fail(ctx, MMPFN_ERR_HIP, "mmpfn_xform_create: upload failed");
+    if (rc != MMPFN_OK) {
+      delete p;
+      return rc;
+    }
+  }
+  *out = p;
+  return MMPFN_OK;
+}
+
+void mmpfn_xform_free(mmpfn_ctx* ctx, mmpfn_xform* prog) {
+  if (!prog) return;
+  if (ctx) {
+    (void)hipSetDevice(ctx->device);
+    for (hipStream_t s : ctx->seen_streams) (void)hipStreamSynchronize(s);
+  }
+  delete prog;
+}
+
+int mmpfn_member_transform(mmpfn_ctx* ctx, const mmpfn_xform* prog, const void* x, int x_is_f64, int Q, int F_in,
+                           int64_t ldx, float* out32, int64_t ld32, double* out64, int64_t ld64) {
+  if (!ctx || !prog) return MMPFN_ERR_INVALID;
+  if (Q < 0 || F_in != prog->n_in || ldx < F_in || ld32 < prog->n_out || (out64 && ld64 < prog->n_out))
+    return fail(ctx, MMPFN_ERR_INVALID, "mmpfn_member_transform: Q < 0, F_in is not the program's input width (" +
+                                            std::to_string(prog->n_in) + "), or a leading dimension below its row");
+  if (Q == 0) return MMPFN_OK;
+  if (!x || !out32) return fail(ctx, MMPFN_ERR_INVALID, "mmpfn_member_transform: null x or out32");
+  HIPCHK(hipSetDevice(ctx->device));
+  RC(ensure_flag(ctx, ctx->ws_flag, ctx->stream));
+  XformArgs a{};
+  a.ops = (const int32_t*)prog->ops.p, a.ints = (const int32_t*)prog->ints.p, a.dbl = (const double*)prog->dbl.p;
+  a.x = x, a.out32 = out32, a.out64 = out64, a.flag = (int*)ctx->ws_flag.p;
+  a.ldx = ldx, a.ld32 = ld32, a.ld64 = ld64;
+  a.x_f64 = x_is_f64 != 0, a.Q = Q, a.n_ops = prog->n_ops, a.n_in = prog->n_in, a.n_out = prog->n_out;
+  a.width = prog->width;
+  HIPCHK(launch_xform(a, ctx->stream));
+  return MMPFN_OK;
+}
+
+static_assert(MMPFN_XFORM_MAX_WIDTH == kXformMaxWidth, "the header's row limit is the kernel's");
+
 int mmpfn_status(mmpfn_ctx* ctx) {
   if (!ctx) return MMPFN_ERR_INVALID;
   HIPCHK(hipSetDevice(ctx->device));
@@ -1211,6 +1328,8 @@ int mmpfn_status(mmpfn_ctx* ctx) {
       HIPCHK(hipMemset(fp, 0, 4));  // reported once; the next forwards start clean
     }
   }
+  if (bad & kXformInfFlag)  // mmpfn_member_transform met +-inf in a device X: validate_X_predict's error on the host path
+    return fail(ctx, MMPFN_ERR_NAN, "Input X contains infinity or a value too large for dtype('float64').");
   if (bad) return fail(ctx, MMPFN_ERR_NAN, "There should be no NaNs in the encoded x and y (flag " + std::to_string(bad) + ")");
   return MMPFN_OK;
 }

@@ -325,6 +325,30 @@ struct BarSampleArgs {
 };
 hipError_t launch_bar_sample(const BarSampleArgs& a, int Q, hipStream_t st);
 
+// Member preprocessing of the test rows (xform.hip xform_kernel): a compiled program (device_transform.py) over rows
+// [0, Q) of x, all arithmetic in float64.  ops [n_ops][kXformOpInts] = (code, width in, width out, int offset, double
+// offset, a, b, c); a kXformMap column is kXformMapInts ints (source, kind, double offset, n, aux).  width: the widest
+// row of the program, at most kXformMaxWidth -- a block keeps xform_rows_per_block(width) rows twice in 64 KiB of LDS.
+// An infinite input cell ORs kXformInfFlag into *flag (the lane's NaN flag word, read by mmpfn_status).
+constexpr int kXformMaxWidth = 4096, kXformMaxRows = 8, kXformThreads = 256, kXformOpInts = 8, kXformMapInts = 5;
+constexpr int kXformGather = 1, kXformMap = 2, kXformSvd = 3, kXformFingerprint = 4;
+constexpr int kXformPass = 0, kXformLookup = 1, kXformQuantile = 2, kXformScale = 3;
+constexpr int kXformInfFlag = 0x100;
+struct XformArgs {
+  const int32_t* ops;
+  const int32_t* ints;
+  const double* dbl;
+  const void* x;  // [Q][ldx] float32, or float64 with x_f64
+  float* out32;   // [Q][ld32]
+  double* out64;  // [Q][ld64] the values before the final rounding, or null
+  int* flag;
+  int64_t ldx, ld32, ld64;
+  int x_f64, Q, n_ops, n_in, n_out, width;
+  int rows;  // set by launch_xform
+};
+int xform_rows_per_block(int width);
+hipError_t launch_xform(const XformArgs& a, hipStream_t st);
+
 // ---- mixer helpers -----------------------------------------------------------------
 hipError_t launch_layernorm_rows(const float* in, int64_t rows, int dim, float eps, void* out, DType out_t,
                                  const float* gamma, const float* beta, hipStream_t st);

@@ -643,9 +643,72 @@ class HipEngine:
         )
         return {**res, **scores}
 
+    def xform_upload(self, program) -> "XformProgram":
+        """A ``device_transform.MemberProgram`` copied to the device (``mmpfn_xform_create``, which checks every
+        index in it); the handle frees the copy when it goes away."""
+        ops = np.ascontiguousarray(program.ops, dtype=np.int32)
+        ints = np.ascontiguousarray(program.ints, dtype=np.int32)
+        dbl = np.ascontiguousarray(program.doubles, dtype=np.float64)
+        h = ctypes.c_void_p()
+        self._check(
+            self.lib.mmpfn_xform_create(self.ctx, ops.ctypes.data, ops.shape[0], ints.ctypes.data, ints.size,
+                                        dbl.ctypes.data, dbl.size, int(program.n_in), ctypes.byref(h)),
+            "mmpfn_xform_create",
+        )
+        return XformProgram(self, h.value, n_in=int(program.n_in), n_out=int(program.n_out))
+
+    def member_transform(self, program, X: torch.Tensor, out: torch.Tensor | None = None, want64: bool = False):
+        """A member's preprocessing of the test rows ``X`` ``[Q, n_in]`` (a float32 or float64 tensor on this device;
+        rows may be strided) on the current stream, one launch (``mmpfn_member_transform``).  ``program``: an
+        ``XformProgram`` of this engine, or a ``MemberProgram`` (uploaded on first use and kept with it).  ``out``:
+        a float32 ``[Q, >= n_out]`` view to write into (say rows ``[N, N + Q)`` of the member's full table), else a
+        new ``[Q, n_out]`` tensor.  Returns ``out``, with ``want64`` ``(out, out64)``, ``out64`` the float64 values
+        before the final rounding (``want64`` may be the float64 ``[Q, >= n_out]`` view to put them in).  A ``+-inf``
+        cell raises sklearn's ``ValueError`` at the next ``status()``."""
+        if not isinstance(program, XformProgram):
+            held = program._handles.get(self.serial)
+            if held is None:
+                held = program._handles[self.serial] = self.xform_upload(program)
+            program = held
+        if program.engine is not self or not program.handle:
+            raise ValueError("the program belongs to another engine or was freed")
+        if not isinstance(X, torch.Tensor) or X.device != self.device or X.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"X must be a float32 or float64 tensor on {self.device}")
+        if X.dim() != 2 or X.shape[1] != program.n_in:
+            raise ValueError(f"X has shape {tuple(X.shape)}, the program takes [Q, {program.n_in}]")
+        if X.stride(1) != 1 or (X.shape[0] > 1 and X.stride(0) < X.shape[1]):
+            X = X.contiguous()
+        Q = X.shape[0]
+        if out is None:
+            out = torch.empty((Q, program.n_out), device=self.device, dtype=torch.float32)
+        if (out.dtype != torch.float32 or out.device != self.device or out.dim() != 2 or out.shape[0] != Q
+                or out.shape[1] < program.n_out or out.stride(1) != 1 or (Q > 1 and out.stride(0) < program.n_out)):
+            raise ValueError(f"out must be a float32 [{Q}, >= {program.n_out}] view with unit column stride")
+        out64 = None
+        if isinstance(want64, torch.Tensor):
+            out64 = want64
+            if (out64.dtype != torch.float64 or out64.device != self.device or out64.dim() != 2 or out64.shape[0] != Q
+                    or out64.shape[1] < program.n_out or out64.stride(1) != 1
+                    or (Q > 1 and out64.stride(0) < program.n_out)):
+                raise ValueError(f"want64 must be a float64 [{Q}, >= {program.n_out}] view with unit column stride")
+        elif want64:
+            out64 = torch.empty((Q, program.n_out), device=self.device, dtype=torch.float64)
+        if Q:
+            self._bind_stream()
+            self._check(
+                self.lib.mmpfn_member_transform(self.ctx, ctypes.c_void_p(program.handle), _ptr(X),
+                                                int(X.dtype == torch.float64), Q, program.n_in,
+                                                X.stride(0) if Q > 1 else program.n_in, _ptr(out),
+                                                out.stride(0) if Q > 1 else out.shape[1], _ptr(out64),
+                                                program.n_out if out64 is None or Q == 1 else out64.stride(0)),
+                "mmpfn_member_transform",
+            )
+        return out if out64 is None else (out, out64)
+
     def status(self) -> None:
         """Wait for every stream the context ran on and raise ``ValueError`` if any forward since the
-        last call saw NaNs in its embedded input (transformer.py:727-731,790-796)."""
+        last call saw NaNs in its embedded input (transformer.py:727-731,790-796), or a member transform an
+        infinity in a device ``X`` (the host path's ``validate_X_predict``)."""
         self._bind_stream()
         self._check(self.lib.mmpfn_status(self.ctx), "mmpfn_forward")
 
@@ -791,6 +854,24 @@ class HipEngine:
         self._bind_stream()
         self._check(self.lib.mmpfn_decode(self.ctx, _ptr(out)), "mmpfn_decode")
         return out
+
+
+class XformProgram:
+    """Device copy of one member's preprocessing program (owned by its engine's context)."""
+
+    def __init__(self, engine: HipEngine, handle: int, *, n_in: int, n_out: int):
+        self.engine, self.handle, self.n_in, self.n_out = engine, handle, n_in, n_out
+
+    def free(self) -> None:
+        if self.handle and getattr(self.engine, "ctx", None):
+            self.engine.lib.mmpfn_xform_free(self.engine.ctx, ctypes.c_void_p(self.handle))
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:  # noqa: BLE001 - interpreter shutdown
+            pass
 
 
 class TrainCache:

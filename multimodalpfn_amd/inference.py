@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 from multimodalpfn_amd import _lib
+from multimodalpfn_amd.device_transform import DeviceTable, compile_member, with_front
 from multimodalpfn_amd.preprocessing import fit_preprocessing
 from multimodalpfn_amd.utils import infer_random_state
 
@@ -106,6 +107,47 @@ class InferenceEngine:
     _pending_status: Any = field(default=None, repr=False)
     _defer_status: bool = field(default=False, repr=False)  # set by a caller that calls check_status() itself
     _early_mixer = False  # executors whose predict runs _run_members with self.model / self.image_train
+    # the members' preprocessing as device programs (device_transform.py), compiled at fit from the fitted pipelines:
+    # member_programs takes the members' input table, device_programs (attach_front) the estimator's raw X.  None: the
+    # member has a step without a device form (program_reasons says which) and keeps the host transform.
+    member_programs: list = field(default_factory=list, repr=False)
+    device_programs: list = field(default_factory=list, repr=False)
+    program_reasons: list = field(default_factory=list, repr=False)
+
+    def compile_programs(self, preprocessors, X_train) -> None:
+        """Compile every fitted member pipeline, probe-checked on the first train rows (``compile_member``)."""
+        self.member_programs, self.program_reasons, self.device_programs = [], [], []
+        for pipe in preprocessors:
+            prog, why = (None, "no table") if pipe is None or X_train is None else \
+                compile_member(pipe, np.asarray(X_train).shape[1], probe=X_train)
+            self.member_programs.append(prog)
+            self.program_reasons.append(why)
+
+    def attach_front(self, plan) -> None:
+        """Put the estimator's front encoder (its ``_ordinal_plan_``) in front of every member program; without a
+        plan no member has a device program."""
+        self.device_programs = []
+        for k, prog in enumerate(self.member_programs):
+            full = None
+            if prog is not None and plan is not None:
+                try:
+                    full = with_front(prog, plan)
+                except ValueError as e:
+                    self.program_reasons[k] = str(e)
+            self.device_programs.append(full)
+
+    def _device_program(self, i: int, eng, cache: dict | None):
+        """Member ``i``'s program on ``eng``'s device (uploaded once, kept in the device cache), or None."""
+        prog = self.device_programs[i] if i < len(self.device_programs) else None
+        if prog is None:
+            return None
+        if cache is None:
+            return prog
+        key = ("xform", i, str(eng.device))
+        held = cache.get(key)
+        if held is None:
+            held = cache[key] = eng.xform_upload(prog)
+        return held
 
     def iter_outputs(self, X, image_test, *, device: torch.device, autocast: bool) -> Iterator[tuple]:
         raise NotImplementedError
@@ -161,20 +203,33 @@ class InferenceEngine:
         # slower per predict at config C (19.1 / 17.5 vs 16.1 / 15.6 ms; default preprocessing 19.7 / 20.1 vs
         # 17.8 / 17.4 ms, profiles/r03/ab/api_transform_inline.txt)
         order = self._launch_order(members, mine)
+        # a table that lives on the GPU: members with a device program transform it there, one launch each on this
+        # stream ahead of their forward; the others get the host transform of its host copy (made once per predict)
+        dev = X if isinstance(X, DeviceTable) else None
+        if dev is not None and any(members[i].X_train is not None and self._device_program(i, eng, cache) is None
+                                   for i in mine):
+            dev.host()  # validated before anything is queued: its errors must not leave members half launched
 
         def items():  # a generator: forward_many launches each unit as soon as its members are ready
             for i in order:
                 m = members[i]
                 x_full = None
                 if m.X_train is not None:
-                    X_test = _h2d(m.preprocessor.transform(X).X, eng.device)
                     key = ("X_train", i, str(eng.device))
                     xtr = None if cache is None else cache.get(key)
                     if xtr is None:
                         xtr = _h2d(m.X_train, eng.device)
                         if cache is not None:
                             cache[key] = xtr
-                    x_full = torch.cat([xtr, X_test], 0)
+                    prog = None if dev is None else self._device_program(i, eng, cache)
+                    if prog is not None:
+                        n = xtr.shape[0]
+                        x_full = torch.empty((n + len(dev), xtr.shape[1]), device=eng.device, dtype=torch.float32)
+                        x_full[:n].copy_(xtr)
+                        eng.member_transform(prog, dev.tensor, out=x_full[n:])
+                    else:
+                        X_test = _h2d(m.preprocessor.transform(X if dev is None else dev.host()).X, eng.device)
+                        x_full = torch.cat([xtr, X_test], 0)
                 yield x_full, tokens, np.asarray(m.y_train, np.float32)
 
         outs: dict[int, torch.Tensor] = dict(zip(order, eng.forward_many(items(), prec)))
@@ -249,9 +304,11 @@ class InferenceEngineCachePreprocessing(InferenceEngine):
         itr = fit_preprocessing(configs=ensemble_configs, X_train=X_train, y_train=y_train, random_state=rng,
                                 cat_ix=cat_ix, n_workers=n_workers, parallel_mode="block")
         configs, preprocessors, X_trains, y_trains, cat_ixs = list(zip(*itr))
-        return cls(save_peak_mem=save_peak_mem, dtype_byte_size=dtype_byte_size, X_trains=X_trains,
-                   y_trains=y_trains, image_train=image_train, cat_ixs=cat_ixs, ensemble_configs=configs,
-                   preprocessors=preprocessors, model=model, force_inference_dtype=force_inference_dtype)
+        ex = cls(save_peak_mem=save_peak_mem, dtype_byte_size=dtype_byte_size, X_trains=X_trains,
+                 y_trains=y_trains, image_train=image_train, cat_ixs=cat_ixs, ensemble_configs=configs,
+                 preprocessors=preprocessors, model=model, force_inference_dtype=force_inference_dtype)
+        ex.compile_programs(preprocessors, X_train)
+        return ex
 
     def members(self) -> list[_Member]:
         return [_Member(c, p, xt, yt, ci) for c, p, xt, yt, ci in
@@ -297,6 +354,8 @@ class InferenceEngineOnDemand(InferenceEngine):
                                 random_state=rng, cat_ix=self.cat_ix, n_workers=self.n_workers,
                                 parallel_mode="in-order")
         members = [_Member(c, p, xt, yt, ci) for c, p, xt, yt, ci in itr]
+        if isinstance(X, DeviceTable):  # the members are re-fitted at every predict: nothing compiled, the host route
+            X = X.host()
         self.model = self.model.to(device)
         outs = self._run_members(members, X, self.image_train, image_test, device=device, autocast=autocast,
                                  forced_dtype=self.force_inference_dtype, model=self.model)
@@ -354,20 +413,32 @@ class InferenceEngineCacheKV(InferenceEngine):
             caches[i] = eng.cache_build(xt, tokens, np.asarray(y_trains[i], np.float32), prec)
         if mine:
             eng.status()  # NaN in the encoded train rows (transformer.py:727-731,790-796)
-        return cls(save_peak_mem=save_peak_mem, dtype_byte_size=dtype_byte_size, caches=caches,
-                   ensemble_configs=configs, preprocessors=preprocessors, n_members=len(configs), model=model,
-                   precision=prec, mine=list(mine), gather=gather)
+        ex = cls(save_peak_mem=save_peak_mem, dtype_byte_size=dtype_byte_size, caches=caches,
+                 ensemble_configs=configs, preprocessors=preprocessors, n_members=len(configs), model=model,
+                 precision=prec, mine=list(mine), gather=gather)
+        ex.compile_programs(preprocessors, X_train)
+        return ex
 
     def iter_outputs(self, X, image_test, *, device: torch.device, autocast: bool) -> Iterator[tuple]:
         eng = self.model.engine(self.model._device() if device.type != "cuda" else device)
         tokens = None
         if image_test is not None and self.model.mixer_type in ("MGM", "MGM+CAP", "MoE") and self.mine:
             tokens = eng.mixer_tokens(torch.from_numpy(np.asarray(image_test, np.float32)), self.precision)
+        dev = X if isinstance(X, DeviceTable) else None
+        cache = self._fresh_cache(self.model, eng) if dev is not None else None
+        if dev is not None and any(self.caches[i].F > 0 and self._device_program(i, eng, cache) is None
+                                   for i in self.mine):
+            dev.host()  # validated before anything is queued
         xts = []
         for i in self.mine:
             xt = None
             if X is not None and self.caches[i].F > 0:
-                xt = torch.from_numpy(np.asarray(self.preprocessors[i].transform(X).X, np.float32))
+                prog = None if dev is None else self._device_program(i, eng, cache)
+                if prog is not None:  # on this stream, ahead of the lanes' forwards
+                    xt = eng.member_transform(prog, dev.tensor)
+                else:
+                    Xh = X if dev is None else dev.host()
+                    xt = torch.from_numpy(np.asarray(self.preprocessors[i].transform(Xh).X, np.float32))
             xts.append(xt)
         outs = dict(zip(self.mine, eng.cache_predict_many([self.caches[i] for i in self.mine], xts, tokens)))
         if self.mine:

@@ -27,6 +27,7 @@ from sklearn.base import BaseEstimator, RegressorMixin, check_is_fitted
 from multimodalpfn_amd.bar_distribution import FullSupportBarDistribution, border_tables
 from multimodalpfn_amd.base import create_inference_engine, determine_precision, initialize_mmpfn_model
 from multimodalpfn_amd.constants import ModelInterfaceConfig
+from multimodalpfn_amd.device_transform import device_table, plan_front_encoder
 from multimodalpfn_amd.model.preprocessing import ReshapeFeatureDistributionsStep
 from multimodalpfn_amd.preprocessing import (
     EnsembleConfig,
@@ -148,6 +149,7 @@ class MMPFNRegressor(RegressorMixin, BaseEstimator):
             enc = _get_ordinal_encoder()
             X = enc.fit_transform(X)
             self.preprocessor_ = enc
+            self._ordinal_plan_ = plan_front_encoder(enc)  # the front encoder's device form (None: string categories)
             self.inferred_categorical_indices_ = infer_categorical_features(
                 X=X,
                 provided=self.categorical_features_indices,
@@ -206,6 +208,8 @@ class MMPFNRegressor(RegressorMixin, BaseEstimator):
             memory_saving_mode=self.memory_saving_mode,
             use_autocast_=self.use_autocast_,
         )
+        if X is not None:
+            self.executor_.attach_front(self._ordinal_plan_)
         return self
 
     # ------------------------------------------------------------------ predict
@@ -245,6 +249,12 @@ class MMPFNRegressor(RegressorMixin, BaseEstimator):
             self._head_tables_ = tables
         return tables
 
+    def _encode_host(self, X) -> np.ndarray:
+        """validate -> _fix_dtypes -> fitted ordinal encoder (``regressor.py:604-607``)."""
+        X = validate_X_predict(X, self)
+        X = _fix_dtypes(X, cat_indices=self.categorical_features_indices)
+        return self.preprocessor_.transform(X)
+
     def predict_device(self, X, image_test: np.ndarray | None, *, quantiles: Sequence[float] = (),
                        want_logits: bool = False, targets=None) -> dict:
         """The head's outputs left on the GPU: ``mean`` / ``mode`` ``[Q]``, ``quantiles`` ``[K, Q]``, ``logits``
@@ -254,10 +264,12 @@ class MMPFNRegressor(RegressorMixin, BaseEstimator):
         ``pi`` and ``ei`` (the target as the incumbent) ``[Q, J]``, and ``mean_of_square`` / ``variance`` ``[Q]`` --
         the ``[Q, B]`` log-probabilities reach memory only with ``want_logits``."""
         check_is_fitted(self)
-        if X is not None:
-            X = validate_X_predict(X, self)
-            X = _fix_dtypes(X, cat_indices=self.categorical_features_indices)
-            X = self.preprocessor_.transform(X)
+        if isinstance(X, torch.Tensor) and X.is_cuda:
+            # a table on the GPU (``[Q, n_features_in_]``, here and in every method built on this one): encoded and
+            # preprocessed there by the members that have a device program (device_transform.py)
+            X = device_table(self, X, self.device_, self._encode_host)
+        elif X is not None:
+            X = self._encode_host(X)
         logits, configs = [], []
         for out, config in self.executor_.iter_outputs(X, image_test=image_test, device=self.device_,
                                                        autocast=self.use_autocast_):
