@@ -52,6 +52,8 @@
  *   mmpfn_item_qkv
  *       <- model/layer.py:341-372's q / k / v projections, train rows (:362-372) and test rows (:344-358):
  *          what precedes the item attention's softmax(QK^T)V
+ *   mmpfn_item_attention_forward
+ *       <- model/layer.py:341-379's softmax(QK^T)V itself, in the three forms the forwards launch it in
  *   mmpfn_mgm / mmpfn_cap
  *       <- model/transformer.py:33-57 MultiheadGatedMLP / :60-88 CrossAttentionPooler
  */
@@ -444,6 +446,26 @@ int mmpfn_outproj_mlp_ln(mmpfn_ctx* ctx, int layer, float* X, const void* O, int
  * nothing is launched then. */
 int mmpfn_item_qkv(mmpfn_ctx* ctx, int layer, const float* X, int S, int T, int N, int M, int last, int precision,
                    void* q, void* k, void* vt);
+/* The item attention's softmax(Q K^T) V alone, launched with the arguments the forwards launch it with (one host
+ * function builds them for the layers and for this tap): what sits between mmpfn_item_qkv and mmpfn_outproj_mlp_ln.
+ *   form 0  a full layer: train rows [0, N) of head h against K / V head h, test rows [N, S) of every head against
+ *           K / V head 0; every row of out is written.  N == S (no test rows) is a cache build's form.
+ *   form 1  the pruned last layer: the test rows, and of the train rows only [N - N % 256, N), which share the test
+ *           rows' first 256-query task; rows [0, N - N % 256) of out are not written.  Needs N < S.
+ *   form 2  a train-KV cache's predict: all S rows are test rows, against a head-0-only k [T][Npad][32] and
+ *           vt [T][32][Npad] of N keys (mmpfn_cache_build's layout); an fp8 code runs the bf16 P.V, as the cache does.
+ * q [T][H][S][32], k [T][H][Npad][32], vt [T][H][32][Npad], out [T][S][H*32], T token columns, keys [0, N), Npad a
+ * multiple of 64 and >= N, H <= 8.  The operands are taken as the forward of the mode takes them: the 16-bit codes read
+ * bf16 q (already times log2(e) / sqrt(32), as mmpfn_item_qkv writes it), bf16 k and vt, and write out in bf16
+ * (MMPFN_PREC_BF16*) or fp16 (MMPFN_PREC_F16*); the fp8 codes convert vt to e4m3 inside; MMPFN_PREC_F32 / _F32_MFMA
+ * read the plain fp32 projection and write fp32.  The precision is decoded as mmpfn_item_attention_block decodes it
+ * (MMPFN_PREC_F16* at T > 64 runs as MMPFN_PREC_BF16*).  q, k and vt are not modified; K rows and V^T columns
+ * [N, Npad) may hold anything.
+ * MMPFN_ERR_INVALID (mmpfn_last_error says which) for a form outside 0..2, an unknown precision, T <= 0, S <= 0,
+ * N <= 0, N > S in forms 0 and 1, N == S in form 1, N > Npad, Npad % 64 != 0, H outside [1, 8]; a null pointer returns
+ * it without a message; nothing is launched then. */
+int mmpfn_item_attention_forward(mmpfn_ctx* ctx, const void* q, const void* k, const void* vt, void* out, int S,
+                                 int T, int H, int Npad, int N, int form, int precision);
 /* modality heads: image [S][n_mod][nhid] -> MGM tokens [S][mgm*n_mod][E] (head-major, as the
  * reference concatenates them); MGM tokens [S][M][E] -> CAP tokens [S][cap][E] */
 int mmpfn_mgm(mmpfn_ctx* ctx, const float* image, int S, int n_mod, float* tokens, int precision);

@@ -132,6 +132,7 @@ SIGNATURES = [
     ("mmpfn_mlp_ln", _i, [_vp, _i, _vp, _i64, _i]),
     ("mmpfn_outproj_mlp_ln", _i, [_vp, _i, _vp, _vp, _i64, _i]),
     ("mmpfn_item_qkv", _i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    ("mmpfn_item_attention_forward", _i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i]),
     ("mmpfn_mgm", _i, [_vp, _vp, _i, _i, _vp, _i]),
     ("mmpfn_cap", _i, [_vp, _vp, _i, _i, _vp, _i]),
     ("mmpfn_kernel_timing_read", _i, [_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64),

@@ -541,6 +541,29 @@ int item_project(mmpfn_ctx* ctx, int l, const void* Xv, int S, int T, int N, int
   return project_qkv(ctx, pm, true, Xv, rows, 2, Q, K, Vt, S, Npad, H);
 }
 
+// ---- the item attention's launch arguments as the forwards build them, in one place: the task map (own-head rows,
+//      shared-KV rows, the cache stride) and the operand form of the mode.  TM token columns of S rows, N train rows
+//      (keys), K / V^T rows padded to Npad; the caller adds the operands' addresses (and the fp8 V^T).
+//      full:   train rows [0, N) against their own heads, test rows [N, S) of every head against head 0's K / V (MQA).
+//      last:   the pruned last layer: of the train rows only those that share the test rows' first 256-query task.
+//      cached: every row is a test row, against a head-0-only K / V^T (column blocks Npad * 32 elements apart).
+//      item_sublayer and the mmpfn_item_attention_forward tap both come here: what the tap launches is what the
+//      forwards launch.
+enum ItemAttnForm { ITEM_ATTN_FULL = 0, ITEM_ATTN_LAST = 1, ITEM_ATTN_CACHED = 2 };
+AttnLayerArgs item_attn_args(ItemAttnForm form, int S, int N, int TM, int H, int Npad, PrecMode pm) {
+  AttnLayerArgs a{nullptr, nullptr, nullptr, nullptr, S, TM, H, Npad, N};
+  if (form == ITEM_ATTN_CACHED) {
+    a.a0 = 0, a.na = 0, a.b0 = 0, a.nb = S, a.kvb = 0;  // every row against head 0 of the cache
+    a.kv_bstride = (int64_t)Npad * 32;
+  } else {
+    // train rows (own heads) and test rows (head-0 K/V, MQA)
+    a.a0 = 0, a.na = N, a.b0 = N, a.nb = S - N, a.kvb = 0;
+    if (form == ITEM_ATTN_LAST) a.na = N % ATTN_ITEM_QPB, a.a0 = N - a.na;
+  }
+  a.q_prescaled = pm.is16(), a.o_t = pm.attn_out();  // (qk_t: bf16 in every forward)
+  return a;
+}
+
 // ---- attention between items (layer.py:341-379) of layer l over the rows of all members (item_project has the row
 //      map).
 //      fuse_out: the out-projection + residual + LN is left to the caller's layer_tail (the attention output
@@ -572,10 +595,8 @@ int item_sublayer(mmpfn_ctx* ctx, int l, void* Xv, int S, int T, int N, int Npad
     const size_t kvl = (size_t)T * cc->Npad * 32 * eb;
     const size_t ccol = (size_t)c0 * cc->Npad * 32 * eb;  // the first column's K (V^T) block inside the layer's
     const unsigned char* Kc = (const unsigned char*)cc->kv.p + (size_t)l * 2 * kvl + ccol;
-    AttnLayerArgs a{Qi, Kc, Kc + kvl, O, S, TM, H, cc->Npad, cc->N};
-    a.a0 = 0, a.na = 0, a.b0 = 0, a.nb = S, a.kvb = 0;  // every row against head 0 of the cache
-    a.kv_bstride = (int64_t)cc->Npad * 32;
-    a.q_prescaled = pm.is16(), a.o_t = pm.attn_out();  // (qk_t: bf16 in every forward)
+    AttnLayerArgs a = item_attn_args(ITEM_ATTN_CACHED, S, cc->N, TM, H, cc->Npad, pm);
+    a.q = Qi, a.k = Kc, a.vt = Kc + kvl, a.out = O;
     HIPCHK(launch_attn_layer(a, pm.base, st));
   } else {
     if (ctx->cache_out) {  // keep head 0's K / V^T of every column (the test rows' KV, layer.py:344-358)
@@ -586,11 +607,8 @@ int item_sublayer(mmpfn_ctx* ctx, int l, void* Xv, int S, int T, int N, int Npad
       HIPCHK(hipMemcpy2DAsync(Kc + kvl, blk, Vi, (size_t)H * blk, blk, nc, hipMemcpyDeviceToDevice, st));
     }
     if (last && Q == 0) return MMPFN_OK;  // (a cache build: nothing reads the last layer's train-row outputs)
-    // train rows (own heads) and test rows (head-0 K/V, MQA)
-    AttnLayerArgs a{Qi, Ki, Vi, O, S, TM, H, Npad, N};
-    a.a0 = 0, a.na = N, a.b0 = N, a.nb = Q, a.kvb = 0;
-    if (last) a.na = N % ATTN_ITEM_QPB, a.a0 = N - a.na;
-    a.q_prescaled = pm.is16(), a.o_t = pm.attn_out();  // (qk_t: bf16 in every forward)
+    AttnLayerArgs a = item_attn_args(last ? ITEM_ATTN_LAST : ITEM_ATTN_FULL, S, N, TM, H, Npad, pm);
+    a.q = Qi, a.k = Ki, a.vt = Vi, a.out = O;
     hipEvent_t* ev = nullptr;
     if (pm.is16()) {  // the live timing and the fp8 P.V exist for the pipelined kernel only
       if (ctx->kt_on && !last) {  // (the roofline's launches all have the full layer's shape)
@@ -1496,6 +1514,31 @@ int mmpfn_item_attention_cached(mmpfn_ctx* ctx, const void* q, const void* k0, c
   if (S <= 0) return fail(ctx, MMPFN_ERR_INVALID, "bad attention geometry");
   a.kv_bstride = (int64_t)Npad * 32;
   HIPCHK(launch_attn_layer(a, PREC_BF16, ctx->stream));
+  return MMPFN_OK;
+}
+
+int mmpfn_item_attention_forward(mmpfn_ctx* ctx, const void* q, const void* k, const void* vt, void* out, int S,
+                                 int T, int H, int Npad, int N, int form, int precision) {
+  if (!ctx) return MMPFN_ERR_INVALID;
+  if (form < ITEM_ATTN_FULL || form > ITEM_ATTN_CACHED) return fail(ctx, MMPFN_ERR_INVALID, "bad attention form");
+  if (!prec_ok(precision)) return fail(ctx, MMPFN_ERR_INVALID, "bad precision");
+  PrecMode pm = decode_prec(precision, T);
+  if (form == ITEM_ATTN_CACHED) pm.f8 = 0;  // the cache keeps bf16 V^T: its test rows run the bf16 P.V (embed_cached)
+  const AttnLayerArgs f = item_attn_args((ItemAttnForm)form, S, N, T, H, Npad, pm);
+  AttnLayerArgs a;
+  // the taps' geometry rules on the forwards' row sets (T <= 0, N <= 0, N > S -- a negative test-row count --, N > Npad)
+  RC(attn_tap_args(ctx, q, k, vt, out, S, T, H, 8, Npad, N, f.a0, f.na, f.b0, f.nb, f.kvb, a));
+  if (form == ITEM_ATTN_LAST && N == S)  // (the forwards launch nothing then: a cache build reads no last-layer output)
+    return fail(ctx, MMPFN_ERR_INVALID, "the last layer's form needs test rows");
+  if (f.na + f.nb <= 0) return fail(ctx, MMPFN_ERR_INVALID, "bad attention geometry");  // (S <= 0 in the cached form)
+  a.kv_bstride = f.kv_bstride, a.q_prescaled = f.q_prescaled, a.o_t = f.o_t;
+  if (pm.is16() && pm.f8) {  // as item_sublayer: e4m3 V^T beside the bf16 one
+    const int64_t n = (int64_t)T * H * 32 * Npad;
+    RC(ensure(ctx, ctx->tap_v8, (size_t)n));
+    HIPCHK(launch_vt_fp8(vt, ctx->tap_v8.p, n, ctx->stream));
+    a.vt8 = ctx->tap_v8.p, a.f8 = pm.f8;
+  }
+  HIPCHK(launch_attn_layer(a, pm.base, ctx->stream));
   return MMPFN_OK;
 }
 
