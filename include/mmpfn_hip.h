@@ -165,6 +165,29 @@ int mmpfn_forward(mmpfn_ctx* ctx, const float* x, int S, int F, const float* tok
  * too (the pruned form's reference and A/B handle); 0, the default, prunes. */
 int mmpfn_set_full_last_layer(mmpfn_ctx* ctx, int on);
 
+/* ---- row embeddings -----------------------------------------------------------------
+ * The reference's forward with only_return_standard_out=False returns, beside the logits, the target token's final
+ * state of every row (transformer.py:850-864): train_embeddings [N][1][E] and test_embeddings [S - N][1][E].
+ * mmpfn_forward_embed is mmpfn_forward with these two as outputs: train_emb [N][E] and test_emb [S - N][E], fp32
+ * on the device, 16-byte aligned (the fp16 state of MMPFN_PREC_F16* widened exactly).  Each of logits, train_emb and
+ * test_emb may be NULL (a NULL logits skips the decoder); all three NULL: MMPFN_ERR_INVALID.  N == S gives a
+ * test_emb of zero rows.
+ *   test_emb alone   the decoder's input rows: what mmpfn_forward launches, plus one gather kernel.
+ *   train_emb        the last layer runs in a third, column form -- the target token's column of all S rows: the
+ *                    feature attention as the pruned form runs it, then the item attention (the full layer's task
+ *                    map on that one column per member), out-projection and MLP of that column alone.  Bit for bit
+ *                    the column a full last layer leaves; with mmpfn_set_full_last_layer(ctx, 1) the last layer
+ *                    runs in full here too.
+ * mmpfn_forward_batch_embed: the same over mmpfn_forward_batch; outputs [M][N][E] and [M][S - N][E].
+ * mmpfn_cache_predict_embed: mmpfn_cache_predict plus test_emb [Q][E], the decoder's input rows of that predict
+ *   (logits or test_emb may be NULL, not both).  The train rows' embeddings of a cache build are not served. */
+int mmpfn_forward_embed(mmpfn_ctx* ctx, const float* x, int S, int F, const float* tokens, int C, const float* y_train,
+                        int N, const float* uniq, int U, const float* pos_rand, float* logits, float* train_emb,
+                        float* test_emb, int precision);
+int mmpfn_forward_batch_embed(mmpfn_ctx* ctx, int M, const float* const* x, int S, int F, const float* tokens, int C,
+                              const float* const* y, int N, const float* const* uniq, const int* U,
+                              const float* pos_rand, float* logits, float* train_emb, float* test_emb, int precision);
+
 /* forward split at its seams (parity taps) */
 int mmpfn_embed(mmpfn_ctx* ctx, const float* x, int S, int F, const float* tokens, int C, const float* y_train, int N,
                 const float* uniq, int U, const float* pos_rand, int precision);
@@ -364,6 +387,9 @@ int mmpfn_cache_build(mmpfn_ctx* ctx, const float* x, int N, int F, const float*
                       const float* uniq, int U, const float* pos_rand, int precision, mmpfn_cache** out);
 int mmpfn_cache_predict(mmpfn_ctx* ctx, const mmpfn_cache* cache, const float* x, int Q, int F, const float* tokens,
                         int C, float* logits);
+/* (row embeddings above) */
+int mmpfn_cache_predict_embed(mmpfn_ctx* ctx, const mmpfn_cache* cache, const float* x, int Q, int F,
+                              const float* tokens, int C, float* logits, float* test_emb);
 int64_t mmpfn_cache_bytes(const mmpfn_cache* cache);
 void mmpfn_cache_free(mmpfn_ctx* ctx, mmpfn_cache* cache);
 

@@ -148,6 +148,10 @@ SIGNATURES = [
     ("mmpfn_xform_create", _i, [_vp, _vp, _i, _vp, _i64, _vp, _i64, _i, ctypes.POINTER(_vp)]),
     ("mmpfn_xform_free", None, [_vp, _vp]),
     ("mmpfn_member_transform", _i, [_vp, _vp, _vp, _i, _i, _i, _i64, _vp, _i64, _vp, _i64]),
+    # mmpfn_forward / mmpfn_forward_batch / mmpfn_cache_predict with the row embeddings as further outputs
+    ("mmpfn_forward_embed", _i, [_vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i]),
+    ("mmpfn_forward_batch_embed", _i, [_vp, _i, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
+    ("mmpfn_cache_predict_embed", _i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp]),
 ]
 
 # include/mmpfn_modality.h (modality encoders: DINOv2 ViT, ELECTRA text tower)

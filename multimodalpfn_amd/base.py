@@ -9,11 +9,55 @@ from __future__ import annotations
 from pathlib import Path
 from typing import Any, Literal
 
+import numpy as np
 import torch
+from sklearn.utils.validation import check_is_fitted
 
 from multimodalpfn_amd.constants import AUTOCAST_DTYPE_BYTE_SIZE, DEFAULT_DTYPE_BYTE_SIZE
-from multimodalpfn_amd.inference import InferenceEngineCacheKV, InferenceEngineCachePreprocessing, InferenceEngineOnDemand
+from multimodalpfn_amd.device_transform import device_table
+from multimodalpfn_amd.inference import (
+    InferenceEngineCacheKV,
+    InferenceEngineCachePreprocessing,
+    InferenceEngineOnDemand,
+    check_embedding_source,
+)
 from multimodalpfn_amd.utils import infer_fp16_inference_mode, load_model_criterion_config
+
+
+class EmbeddingsMixin:
+    """``get_embeddings`` of both estimators (TabPFN's method of that name): every member's row embeddings, the
+    target token's final state of each row, which the forward returns beside the logits.  The estimator supplies
+    ``_encode_for_predict`` (its host encoding of a predict table)."""
+
+    def get_embeddings_device(self, X, image_test: np.ndarray | None,
+                              data_source: Literal["test", "train"] = "test") -> torch.Tensor:
+        """``[n_members, rows, emsize]`` fp32 left on the GPU, members in the order of the ensemble configs.
+
+        ``data_source="test"``: the embeddings of the rows of ``X`` / ``image_test`` (``X`` as ``predict`` takes it:
+        an array, a DataFrame or a CUDA tensor on the estimator's device).  ``"train"``: those of the fitted train
+        rows; ``X`` only rides along as the forward's test rows, which no train row reads, so the result does not
+        depend on it.  ``fit_mode="fit_with_cache"`` serves ``"test"`` only: its cache keeps the train rows' keys
+        and values, not their embeddings."""
+        check_embedding_source(data_source, cached=getattr(self, "fit_mode", None) == "fit_with_cache", required=True)
+        check_is_fitted(self)
+        ex = self.executor_
+        try:
+            if image_test is not None:
+                ex.launch_mixer_early(image_test, device=self.device_, autocast=self.use_autocast_)
+            if isinstance(X, torch.Tensor) and X.is_cuda:
+                X = device_table(self, X, self.device_, self._encode_for_predict)
+            elif X is not None:
+                X = self._encode_for_predict(X)
+            outs = [out for out, _ in ex.iter_outputs(X, image_test=image_test, device=self.device_,
+                                                      autocast=self.use_autocast_, embeddings=data_source)]
+        finally:
+            ex._early_tokens = None
+        return torch.stack(outs)
+
+    def get_embeddings(self, X, image_test: np.ndarray | None,
+                       data_source: Literal["test", "train"] = "test") -> np.ndarray:
+        """``get_embeddings_device`` as a float32 array ``[n_members, rows, emsize]``."""
+        return self.get_embeddings_device(X, image_test, data_source).cpu().numpy()
 
 
 def initialize_mmpfn_model(

@@ -23,7 +23,12 @@ import torch
 from sklearn.base import BaseEstimator, ClassifierMixin, check_is_fitted
 from sklearn.preprocessing import LabelEncoder
 
-from multimodalpfn_amd.base import create_inference_engine, determine_precision, initialize_mmpfn_model
+from multimodalpfn_amd.base import (
+    EmbeddingsMixin,
+    create_inference_engine,
+    determine_precision,
+    initialize_mmpfn_model,
+)
 from multimodalpfn_amd.constants import (
     PROBABILITY_EPSILON_ROUND_ZERO,
     SKLEARN_16_DECIMAL_PRECISION,
@@ -43,7 +48,7 @@ from multimodalpfn_amd.utils import (
 )
 
 
-class MMPFNClassifier(ClassifierMixin, BaseEstimator):
+class MMPFNClassifier(EmbeddingsMixin, ClassifierMixin, BaseEstimator):
     """Multimodal PFN classifier (tabular + image/text embeddings), MI355X engine."""
 
     def __init__(
@@ -244,6 +249,8 @@ class MMPFNClassifier(ClassifierMixin, BaseEstimator):
             return out
         X = _fix_dtypes(X, cat_indices=self.categorical_features_indices)
         return self.preprocessor_.transform(X)
+
+    _encode_for_predict = _encode_predict_X  # (EmbeddingsMixin)
 
     def _plan_ordinal(self) -> None:
         """Record the fitted encoder's column plan for the numpy predict path (or None)."""

@@ -574,8 +574,10 @@ AttnLayerArgs item_attn_args(ItemAttnForm form, int S, int N, int TM, int H, int
 //      of its queries only the test rows; the out-projection is left to the caller.  The test rows keep the places
 //      they have in the full launch's 256-query tasks (the train rows that share their first task ride along), so
 //      every block that holds one sees the same queries and takes the same wave-wide re-run decisions as there.
+//      last && all_rows: the column form (last_layer_column): the same one column per member, every query of it --
+//      the full task map on M columns, so column T-1's queries sit in the 256-query tasks they have in the full layer.
 int item_sublayer(mmpfn_ctx* ctx, int l, void* Xv, int S, int T, int N, int Npad, int M, PrecMode pm, bool fuse_out,
-                  bool last = false) {
+                  bool last = false, bool all_rows = false) {
   const mmpfn_model_desc& d = ctx->d;
   const LayerW& L = ctx->w.layers[l];
   const int E = d.emsize, H = d.nhead, Q = S - N;
@@ -606,8 +608,8 @@ int item_sublayer(mmpfn_ctx* ctx, int l, void* Xv, int S, int T, int N, int Npad
       HIPCHK(hipMemcpy2DAsync(Kc, blk, Ki, (size_t)H * blk, blk, nc, hipMemcpyDeviceToDevice, st));
       HIPCHK(hipMemcpy2DAsync(Kc + kvl, blk, Vi, (size_t)H * blk, blk, nc, hipMemcpyDeviceToDevice, st));
     }
-    if (last && Q == 0) return MMPFN_OK;  // (a cache build: nothing reads the last layer's train-row outputs)
-    AttnLayerArgs a = item_attn_args(last ? ITEM_ATTN_LAST : ITEM_ATTN_FULL, S, N, TM, H, Npad, pm);
+    if (last && !all_rows && Q == 0) return MMPFN_OK;  // (a cache build: nothing reads the last layer's train-row outputs)
+    AttnLayerArgs a = item_attn_args(last && !all_rows ? ITEM_ATTN_LAST : ITEM_ATTN_FULL, S, N, TM, H, Npad, pm);
     a.q = Qi, a.k = Ki, a.vt = Vi, a.out = O;
     hipEvent_t* ev = nullptr;
     if (pm.is16()) {  // the live timing and the fp8 P.V exist for the pipelined kernel only
@@ -677,6 +679,10 @@ int run_layer(mmpfn_ctx* ctx, int l) {
   return layer_tail(ctx, L, Xall, ctx->ws_O.p, (int64_t)S * T * M, pm);
 }
 
+// The last layer has three forms: run_layer (in full: the taps, and the forwards under mmpfn_set_full_last_layer),
+// last_layer_tail (what the decoder reads: every forward by default) and last_layer_column (what the train rows'
+// embeddings need besides: mmpfn_forward_embed with train_emb, and nothing else).
+//
 // The last layer of a forward, pruned to what the decoder reads: the test rows [N, S) of the target token (column
 // T-1) of every member.  Exact, since every kernel computes a state row from that row's own inputs:
 //   feature attention   every row (a test row's target token attends over the row's tokens; a train row's is the
@@ -703,10 +709,38 @@ int last_layer_tail(mmpfn_ctx* ctx, int l) {
   return MMPFN_OK;
 }
 
-// every layer of a forward entry point: the last one pruned unless mmpfn_set_full_last_layer asked for it in full
-int run_forward_layers(mmpfn_ctx* ctx) {
+// The last layer of a forward that returns the train rows' embeddings (mmpfn_forward_embed with train_emb): the
+// column form, the target-token column T-1 of every member, all S rows.  last_layer_tail with the train rows kept:
+//   feature attention   as there (token T-1 of every row);
+//   item attention      column T-1 only, Q of all its rows, the full layer's task map on M columns (item_sublayer,
+//                       last and all_rows) -- the launch of a full layer that had no other column;
+//   out-projection, MLP the S rows of that column, member by member, O compact [M][S][E].
+// Exact for the same reason, so column T-1 afterwards holds what run_layer leaves there bit for bit; the other
+// columns are left as last_layer_tail leaves them.
+int last_layer_column(mmpfn_ctx* ctx, int l) {
+  const LayerW& L = ctx->w.layers[l];
+  const int S = ctx->S, T = ctx->T, N = ctx->N, Npad = ctx->Npad, M = ctx->M, E = ctx->d.emsize;
+  const PrecMode pm = lane_prec(*ctx);
+  RC(feat_sublayer(ctx, L, ctx->ws_X.p, S, T, M, pm, true));
+  RC(item_sublayer(ctx, l, ctx->ws_X.p, S, T, N, Npad, M, pm, true, true, true));
+  const size_t ob = pm.op_bytes();
+  for (int m = 0; m < M; ++m) {
+    void* X = (char*)ctx->ws_X.p + ((size_t)m * T + T - 1) * S * E * pm.state_bytes();
+    const void* O = (const char*)ctx->ws_O.p + (size_t)m * S * E * ob;
+    RC(layer_tail(ctx, L, X, O, S, pm));
+  }
+  return MMPFN_OK;
+}
+
+// every layer of a forward entry point: the last one pruned -- to the test rows of the target token, or with
+// `column` (a forward that returns the train rows' embeddings) to all of its rows -- unless
+// mmpfn_set_full_last_layer asked for it in full
+int run_forward_layers(mmpfn_ctx* ctx, bool column = false) {
   const int nl = ctx->d.nlayers;
-  for (int l = 0; l < nl; ++l) RC(l == nl - 1 && !ctx->full_last ? last_layer_tail(ctx, l) : run_layer(ctx, l));
+  for (int l = 0; l < nl; ++l) {
+    if (l < nl - 1 || ctx->full_last) RC(run_layer(ctx, l));
+    else RC(column ? last_layer_column(ctx, l) : last_layer_tail(ctx, l));
+  }
   return MMPFN_OK;
 }
 
@@ -747,6 +781,32 @@ int decode(mmpfn_ctx* ctx, float* logits, int M = 1) {
                         (const float*)w.dec_w2.f32.p, (const float*)w.dec_b2.p, d.n_out, logits, E, ctx->stream, M,
                         xm, (int64_t)Q * d.n_out, (float*)ctx->ws_O.p));
   return MMPFN_OK;
+}
+
+// rows [r0, r0 + n) of the target token's final state of the lane's M members -> out fp32 [M][n][E]: the train rows'
+// embeddings (r0 = 0, n = N) or the test rows' (r0 = N, n = S - N), transformer.py:850-864
+int target_rows(mmpfn_ctx* ctx, int r0, int n, float* out) {
+  HIPCHK(launch_target_rows(ctx->ws_X.p, lane_prec(*ctx).state(), ctx->S, ctx->T, ctx->d.emsize, ctx->M, r0, n, out,
+                            ctx->stream));
+  return MMPFN_OK;
+}
+
+// what the embedding entry points refuse before anything is launched
+int check_outputs(mmpfn_ctx* ctx, const char* who, const float* logits, const float* train_emb, const float* test_emb) {
+  if (!logits && !train_emb && !test_emb) return fail(ctx, MMPFN_ERR_INVALID, std::string(who) + ": no output asked for");
+  if (((uintptr_t)train_emb | (uintptr_t)test_emb) % 16 != 0)
+    return fail(ctx, MMPFN_ERR_INVALID, std::string(who) + ": the embedding outputs must be 16-byte aligned");
+  return MMPFN_OK;
+}
+
+// the layers, the embeddings and the decoder of a forward whose members are embedded (mmpfn_forward_embed and its
+// batch and cache forms); null outputs are skipped, train_emb alone selects the column form of the last layer
+int forward_outputs(mmpfn_ctx* ctx, float* logits, float* train_emb, float* test_emb, int M) {
+  RC(run_forward_layers(ctx, train_emb != nullptr));
+  // (before the decoder: one of its forms converts the fp16 test rows through the big workspace, none writes the state)
+  if (train_emb) RC(target_rows(ctx, 0, ctx->N, train_emb));
+  if (test_emb) RC(target_rows(ctx, ctx->N, ctx->S - ctx->N, test_emb));
+  return logits ? decode(ctx, logits, M) : MMPFN_OK;
 }
 
 // MGM head bank (transformer.py:33-57): image [S][n_mod][D] -> tokens [S][mgm*n_mod][E] (head-major)
@@ -1089,6 +1149,30 @@ int mmpfn_forward_batch(mmpfn_ctx* ctx, int M, const float* const* x, int S, int
              precision, m, M));
   RC(run_forward_layers(ctx));
   return decode(ctx, logits, M);
+}
+
+int mmpfn_forward_embed(mmpfn_ctx* ctx, const float* x, int S, int F, const float* tokens, int C, const float* y, int N,
+                        const float* uniq, int U, const float* pos_rand, float* logits, float* train_emb,
+                        float* test_emb, int precision) {
+  if (!ctx) return MMPFN_ERR_INVALID;
+  RC(check_outputs(ctx, "mmpfn_forward_embed", logits, train_emb, test_emb));
+  HIPCHK(hipSetDevice(ctx->device));
+  RC(embed(ctx, x, S, F, tokens, C, y, N, uniq, U, pos_rand, precision));
+  return forward_outputs(ctx, logits, train_emb, test_emb, 1);
+}
+
+int mmpfn_forward_batch_embed(mmpfn_ctx* ctx, int M, const float* const* x, int S, int F, const float* tokens, int C,
+                              const float* const* y, int N, const float* const* uniq, const int* U,
+                              const float* pos_rand, float* logits, float* train_emb, float* test_emb, int precision) {
+  const bool codes = ctx && ctx->d.target_kind == MMPFN_TARGET_CLASS;  // a value target reads neither uniq nor U
+  if (!ctx || M <= 0 || !y || (codes && (!uniq || !U))) return MMPFN_ERR_INVALID;
+  if (F > 0 && !x) return MMPFN_ERR_INVALID;
+  RC(check_outputs(ctx, "mmpfn_forward_batch_embed", logits, train_emb, test_emb));
+  HIPCHK(hipSetDevice(ctx->device));
+  for (int m = 0; m < M; ++m)
+    RC(embed(ctx, F > 0 ? x[m] : nullptr, S, F, tokens, C, y[m], N, codes ? uniq[m] : nullptr, codes ? U[m] : 0, pos_rand,
+             precision, m, M));
+  return forward_outputs(ctx, logits, train_emb, test_emb, M);
 }
 
 int mmpfn_state_tokens(const mmpfn_ctx* ctx) { return ctx ? ctx->T : 0; }
@@ -1435,6 +1519,19 @@ int mmpfn_cache_predict(mmpfn_ctx* ctx, const mmpfn_cache* cache, const float* x
   ctx->cache_in = nullptr;
   if (rc) return rc;
   return decode(ctx, logits);
+}
+
+int mmpfn_cache_predict_embed(mmpfn_ctx* ctx, const mmpfn_cache* cache, const float* x, int Q, int F,
+                              const float* tokens, int C, float* logits, float* test_emb) {
+  if (!ctx || !cache) return MMPFN_ERR_INVALID;
+  RC(check_outputs(ctx, "mmpfn_cache_predict_embed", logits, nullptr, test_emb));
+  HIPCHK(hipSetDevice(ctx->device));
+  RC(embed_cached(ctx, cache, x, Q, F, tokens, C));
+  ctx->cache_in = cache;
+  // every row of the state is a test row (N = 0): the pruned last layer as it is, then its rows
+  const int rc = forward_outputs(ctx, logits, nullptr, test_emb, 1);
+  ctx->cache_in = nullptr;
+  return rc;
 }
 
 int64_t mmpfn_cache_bytes(const mmpfn_cache* cache) {

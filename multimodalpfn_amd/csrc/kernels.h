@@ -254,6 +254,11 @@ hipError_t launch_f32_to_f16(const float* in, int64_t in_bstride, void* out, int
 hipError_t launch_f16_to_f32(const void* in, int64_t in_bstride, float* out, int64_t out_bstride, int64_t per_block,
                              int nb, hipStream_t st);
 hipError_t launch_state_f16_to_f32(const void* X, float* out, int S, int T, int E, hipStream_t st);
+// Row embeddings (embrows.hip): rows [r0, r0 + n) of the target token's column T-1 of M members' states
+// X [M][T][S][E] (x_t: fp32 or fp16) -> out fp32 [M][n][E], 16 bytes of the state per thread; X and out 16-byte
+// aligned, E % 8 == 0
+hipError_t launch_target_rows(const void* X, DType x_t, int S, int T, int E, int M, int r0, int n, float* out,
+                              hipStream_t st);
 
 hipError_t launch_aggregate(const float* logits /*[M][Q][n_out]*/, int M, int Q, int n_out,
                             const int* perms /*[M][n_cls] or null*/, int n_cls, float temp, int avg_before,

@@ -252,13 +252,50 @@ class HipEngine:
         yd = self._dev(torch.from_numpy(y_np))
         return xd, td, yd, uniq, S, F, C, N, G
 
-    def forward(self, x, tokens, y_train, precision: int, check_nan: bool = True) -> torch.Tensor:
-        """One ensemble member: logits ``[S - N, n_out]`` (fp32, on the engine device)."""
+    # ``embeddings=`` of the forward entry points -> (train rows' wanted, test rows' wanted)
+    EMBEDDINGS = {"test": (False, True), "train": (True, False), "both": (True, True)}
+
+    @classmethod
+    def _check_embeddings(cls, embeddings) -> None:
+        if embeddings is not None and embeddings not in cls.EMBEDDINGS:
+            raise ValueError(f"embeddings must be None or one of {sorted(cls.EMBEDDINGS)}, got {embeddings!r}")
+
+    def _embedding_outputs(self, embeddings: str, lead: tuple, N: int, Q: int):
+        """The row-embedding outputs ``embeddings`` asks for, fp32 ``[*lead, N, E]`` / ``[*lead, Q, E]`` or None."""
+        self._check_embeddings(embeddings)
+        want_train, want_test = self.EMBEDDINGS[embeddings]
+        E = self.cfg.emsize
+        tr = torch.empty(lead + (N, E), device=self.device, dtype=torch.float32) if want_train else None
+        te = torch.empty(lead + (Q, E), device=self.device, dtype=torch.float32) if want_test else None
+        return tr, te
+
+    def forward(self, x, tokens, y_train, precision: int, check_nan: bool = True, embeddings: str | None = None):
+        """One ensemble member: logits ``[S - N, n_out]`` (fp32, on the engine device).
+
+        ``embeddings``: ``"test"``, ``"train"`` or ``"both"`` returns ``(logits, train_emb, test_emb)`` instead
+        (``mmpfn_forward_embed``): the target token's final state of the train rows ``[N, E]`` and of the test rows
+        ``[S - N, E]``, fp32, the one not asked for None (the reference's ``train_embeddings`` / ``test_embeddings``,
+        transformer.py:850-864).  The logits are those of the plain call bit for bit."""
+        self._check_embeddings(embeddings)
         xd, td, yd, uniq, S, F, C, N, G = self._prepare(x, tokens, y_train)
         if N < 1 or N > S:
             raise ValueError(f"single_eval_pos must be in [1, {S}], got {N}")
         pr = self._pos(G + C)
         out = torch.empty((S - N, self.cfg.n_out), device=self.device, dtype=torch.float32)
+        if embeddings is not None:
+            tr, te = self._embedding_outputs(embeddings, (), N, S - N)
+            self._bind_stream()
+            if _count(out) or _count(tr) or _count(te):  # (an output of no rows has no address: it is not asked for)
+                self._check(
+                    self.lib.mmpfn_forward_embed(
+                        self.ctx, _ptr(xd), S, F, _ptr(td), C, _ptr(yd), N, _ptr(uniq), _count(uniq), _ptr(pr),
+                        _ptr(out) or None, _ptr(tr) or None, _ptr(te) or None, precision,
+                    ),
+                    "mmpfn_forward_embed",
+                )
+            if check_nan:
+                self.status()
+            return out, tr, te
         self._bind_stream()
         self._check(
             self.lib.mmpfn_forward(
@@ -289,11 +326,17 @@ class HipEngine:
         )
         return TrainCache(self, h.value, N=N, F=F, C=C, precision=precision)
 
-    def cache_predict(self, cache: "TrainCache", x, tokens) -> torch.Tensor:
+    def cache_predict(self, cache: "TrainCache", x, tokens, embeddings: str | None = None):
         """Test rows against a train-KV cache: logits ``[Q, n_out]`` (``mmpfn_cache_predict``;
-        reference ``InferenceEngineCacheKV.iter_outputs``, inference.py:470-512)."""
+        reference ``InferenceEngineCacheKV.iter_outputs``, inference.py:470-512).  ``embeddings="test"``:
+        ``(logits, None, test_emb [Q, E])`` as ``forward`` returns them (``mmpfn_cache_predict_embed``); a cache
+        holds no train rows' embeddings."""
         if cache.engine is not self or not cache.handle:
             raise ValueError("the cache belongs to another engine or was freed")
+        if embeddings is not None and embeddings != "test":
+            if embeddings in self.EMBEDDINGS:
+                raise ValueError(f"a train-KV cache serves embeddings='test' only, got {embeddings!r}")
+            raise ValueError(f"embeddings must be None or 'test', got {embeddings!r}")
         xd = None if x is None else self._dev(x)
         if xd is not None and xd.dim() == 3:
             xd = xd.reshape(xd.shape[0], xd.shape[-1])
@@ -304,7 +347,17 @@ class HipEngine:
         if (F, C) != (cache.F, cache.C):
             raise ValueError(f"test rows have F={F}, C={C}; the cache was built with F={cache.F}, C={cache.C}")
         out = torch.empty((Q, self.cfg.n_out), device=self.device, dtype=torch.float32)
+        self._S = Q  # copy_state's row count: every row of a cache predict's state is a test row
         self._bind_stream()
+        if embeddings is not None:
+            _, te = self._embedding_outputs(embeddings, (), 0, Q)
+            if _count(out) or _count(te):  # (an output of no rows has no address: it is not asked for)
+                self._check(
+                    self.lib.mmpfn_cache_predict_embed(self.ctx, ctypes.c_void_p(cache.handle), _ptr(xd), Q, F,
+                                                       _ptr(td), C, _ptr(out) or None, _ptr(te) or None),
+                    "mmpfn_cache_predict_embed",
+                )
+            return out, None, te
         self._check(
             self.lib.mmpfn_cache_predict(self.ctx, ctypes.c_void_p(cache.handle), _ptr(xd), Q, F, _ptr(td), C,
                                          _ptr(out)),
@@ -312,13 +365,15 @@ class HipEngine:
         )
         return out
 
-    def cache_predict_many(self, caches, xs, tokens, lanes: int | None = None) -> list[torch.Tensor]:
+    def cache_predict_many(self, caches, xs, tokens, lanes: int | None = None, embeddings: str | None = None) -> list:
         """``cache_predict`` of several members, spread over concurrent lanes like ``forward_many``
-        (2 lanes: 4.5 ms vs 6.7 ms for 4 members' 460 test rows; 4 lanes measured no better)."""
+        (2 lanes: 4.5 ms vs 6.7 ms for 4 members' 460 test rows; 4 lanes measured no better).  ``embeddings``: as
+        ``cache_predict`` takes it, every member's result then its tuple."""
         n = len(caches)
         lanes = max(1, min(int(self.lanes if lanes is None else lanes), n, _lib.MMPFN_MAX_LANES))
+        kw = {} if embeddings is None else {"embeddings": embeddings}
         if lanes == 1:
-            return [self.cache_predict(c, x, tokens) for c, x in zip(caches, xs)]
+            return [self.cache_predict(c, x, tokens, **kw) for c, x in zip(caches, xs)]
         main = torch.cuda.current_stream(self.device)
         streams = self._lane_streams(lanes)
         for st in streams:
@@ -328,18 +383,23 @@ class HipEngine:
             for k, (c, x) in enumerate(zip(caches, xs)):
                 with torch.cuda.stream(streams[k % lanes]):
                     self._check(self.lib.mmpfn_select_lane(self.ctx, k % lanes), "mmpfn_select_lane")
-                    outs.append(self.cache_predict(c, x, tokens))
+                    outs.append(self.cache_predict(c, x, tokens, **kw))
         finally:
             self._check(self.lib.mmpfn_select_lane(self.ctx, 0), "mmpfn_select_lane")
             for st in streams:
                 main.wait_stream(st)
         for o in outs:
-            o.record_stream(main)
+            for t in (o if isinstance(o, tuple) else (o,)):
+                if t is not None:
+                    t.record_stream(main)
         return outs
 
-    def forward_batch(self, items, precision: int) -> list[torch.Tensor]:
+    def forward_batch(self, items, precision: int, embeddings: str | None = None) -> list:
         """Members of ONE geometry (same S, N, F and tokens) in one batched forward
-        (``mmpfn_forward_batch``: every layer kernel runs once over all members)."""
+        (``mmpfn_forward_batch``: every layer kernel runs once over all members).  ``embeddings``: as ``forward``
+        takes it, every member's result then its ``(logits, train_emb, test_emb)``
+        (``mmpfn_forward_batch_embed``)."""
+        self._check_embeddings(embeddings)
         prep = [self._prepare(x, t, y) for x, t, y in items]
         M = len(prep)
         xd0, td, _, _, S, F, C, N, G = prep[0]
@@ -356,6 +416,17 @@ class HipEngine:
         us = arr(*[_ptr(p[3]) for p in prep])
         ns = (ctypes.c_int * M)(*[_count(p[3]) for p in prep])
         self._bind_stream()
+        if embeddings is not None:
+            tr, te = self._embedding_outputs(embeddings, (M,), N, S - N)
+            if _count(out) or _count(tr) or _count(te):
+                self._check(
+                    self.lib.mmpfn_forward_batch_embed(self.ctx, M, xs, S, F, _ptr(td), C, ys, N, us, ns, _ptr(pr),
+                                                       _ptr(out) or None, _ptr(tr) or None, _ptr(te) or None,
+                                                       precision),
+                    "mmpfn_forward_batch_embed",
+                )
+            none = [None] * M
+            return list(zip(out.unbind(0), none if tr is None else tr.unbind(0), none if te is None else te.unbind(0)))
         self._check(
             self.lib.mmpfn_forward_batch(self.ctx, M, xs, S, F, _ptr(td), C, ys, N, us, ns, _ptr(pr), _ptr(out),
                                          precision),
@@ -364,7 +435,7 @@ class HipEngine:
         return list(out.unbind(0))
 
     def forward_many(self, items, precision: int, lanes: int | None = None,
-                     batch: int | None = None) -> list[torch.Tensor]:
+                     batch: int | None = None, embeddings: str | None = None) -> list:
         """Independent ensemble members ``[(x, tokens, y_train), ...]`` -> logits list.
 
         Members are spread over ``lanes`` forward lanes (per-member workspaces of the same
@@ -374,8 +445,11 @@ class HipEngine:
         its members have arrived, so the caller's host work for later members (the per-member
         preprocessing of a predict) overlaps the GPU work of earlier ones.  The caller's stream
         waits for all of them.  The reference runs its members one after another
-        (inference.py:294-349); the results do not depend on lanes or batching.
+        (inference.py:294-349); the results do not depend on lanes or batching.  ``embeddings``: as ``forward``
+        takes it, every member's result then its ``(logits, train_emb, test_emb)``.
         """
+        self._check_embeddings(embeddings)
+        kw = {} if embeddings is None else {"embeddings": embeddings}
         batch = max(1, int(self.batch if batch is None else batch))
         if isinstance(items, (list, tuple)):
             n_units = len({self._geometry(*it) for it in items})  # lower bound on the unit count
@@ -383,15 +457,15 @@ class HipEngine:
         else:
             n_units = _lib.MMPFN_MAX_LANES
         lanes = max(1, min(int(self.lanes if lanes is None else lanes), n_units, _lib.MMPFN_MAX_LANES))
-        outs: dict[int, torch.Tensor] = {}
+        outs: dict = {}
         store: dict[int, tuple] = {}
 
         def run(unit, stream=None):
             if len(unit) == 1:
                 x, t, y = store[unit[0]]
-                outs[unit[0]] = self.forward(x, t, y, precision, check_nan=False)
+                outs[unit[0]] = self.forward(x, t, y, precision, check_nan=False, **kw)
             else:
-                for i, o in zip(unit, self.forward_batch([store[i] for i in unit], precision)):
+                for i, o in zip(unit, self.forward_batch([store[i] for i in unit], precision, **kw)):
                     outs[i] = o
             if stream is not None:
                 # the unit's device inputs were made on the caller's stream (e.g. each member's
@@ -445,7 +519,9 @@ class HipEngine:
         result = [outs[i] for i in range(n)]
         if lanes > 1:
             for o in result:  # allocated on a lane stream, consumed on the caller's
-                o.record_stream(main)
+                for t in (o if isinstance(o, tuple) else (o,)):
+                    if t is not None:
+                        t.record_stream(main)
         return result
 
     def _geometry(self, x, tokens, y_train) -> tuple:

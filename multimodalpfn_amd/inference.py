@@ -93,9 +93,25 @@ class _Member:
     cat_ix: list[int] | None
 
 
+EMBEDDING_SOURCES = ("test", "train")  # ``embeddings=`` of iter_outputs: whose rows' embeddings the members return
+
+
+def check_embedding_source(embeddings, cached: bool = False, required: bool = False) -> None:
+    """``ValueError`` for an ``embeddings`` that ``iter_outputs`` does not serve; ``cached``: a train-KV cache executor;
+    ``required``: ``None`` (the executors' "the logits, no embeddings") is no answer either (``get_embeddings``)."""
+    if embeddings is None and not required:
+        return
+    if embeddings not in EMBEDDING_SOURCES:
+        raise ValueError(f"data_source must be one of {EMBEDDING_SOURCES}, got {embeddings!r}")
+    if cached and embeddings == "train":
+        raise ValueError("fit_mode='fit_with_cache' keeps the train rows' keys and values, not their embeddings: "
+                         "data_source='train' needs fit_mode='fit_preprocessors' or 'low_memory'")
+
+
 @dataclass
 class InferenceEngine:
-    """Base: ``iter_outputs`` yields ``(logits [Q, n_out], member config)`` per member."""
+    """Base: ``iter_outputs`` yields ``(logits [Q, n_out], member config)`` per member -- with ``embeddings="test"``
+    or ``"train"`` instead of the logits those rows' embeddings ``[rows, E]`` (the target token's final state)."""
 
     save_peak_mem: bool | Literal["auto"] | float | int
     dtype_byte_size: int
@@ -149,7 +165,8 @@ class InferenceEngine:
             held = cache[key] = eng.xform_upload(prog)
         return held
 
-    def iter_outputs(self, X, image_test, *, device: torch.device, autocast: bool) -> Iterator[tuple]:
+    def iter_outputs(self, X, image_test, *, device: torch.device, autocast: bool,
+                     embeddings: str | None = None) -> Iterator[tuple]:
         raise NotImplementedError
 
     def launch_mixer_early(self, image_test, *, device: torch.device, autocast: bool) -> None:
@@ -182,8 +199,10 @@ class InferenceEngine:
 
     # -- shared member loop -------------------------------------------------------
     def _run_members(self, members: Sequence[_Member], X, image_train, image_test, *, device, autocast,
-                     forced_dtype, model) -> list[torch.Tensor]:
+                     forced_dtype, model, embeddings: str | None = None) -> list[torch.Tensor]:
         from multimodalpfn_amd.parallel import member_shard
+
+        check_embedding_source(embeddings)
 
         eng = model.engine(model._device() if device.type != "cuda" else device)
         prec = _precision(model, eng.device, autocast, forced_dtype)
@@ -232,7 +251,11 @@ class InferenceEngine:
                         x_full = torch.cat([xtr, X_test], 0)
                 yield x_full, tokens, np.asarray(m.y_train, np.float32)
 
-        outs: dict[int, torch.Tensor] = dict(zip(order, eng.forward_many(items(), prec)))
+        if embeddings is None:
+            outs: dict[int, torch.Tensor] = dict(zip(order, eng.forward_many(items(), prec)))
+        else:  # (logits, train rows' embeddings, test rows' embeddings) of every member: the one asked for
+            pick = 1 if embeddings == "train" else 2
+            outs = {i: o[pick] for i, o in zip(order, eng.forward_many(items(), prec, embeddings=embeddings))}
         if mine:
             if self._defer_status:
                 # the caller enqueues its own device work (the aggregation) first and then calls check_status():
@@ -241,6 +264,8 @@ class InferenceEngine:
             else:
                 eng.status()  # NaN / HIP errors of every queued member (transformer.py:727-731,790-796)
         Q = len(X) if X is not None else len(image_test)
+        if embeddings is not None:
+            return gather(outs, eng.device, len(members[0].y_train) if embeddings == "train" else Q, model.cfg.emsize)
         return gather(outs, eng.device, Q, model.cfg.n_out)
 
     def check_status(self) -> None:
@@ -314,10 +339,13 @@ class InferenceEngineCachePreprocessing(InferenceEngine):
         return [_Member(c, p, xt, yt, ci) for c, p, xt, yt, ci in
                 zip(self.ensemble_configs, self.preprocessors, self.X_trains, self.y_trains, self.cat_ixs)]
 
-    def iter_outputs(self, X, image_test, *, device: torch.device, autocast: bool) -> Iterator[tuple]:
+    def iter_outputs(self, X, image_test, *, device: torch.device, autocast: bool,
+                     embeddings: str | None = None) -> Iterator[tuple]:
+        check_embedding_source(embeddings)
         self.model = self.model.to(device)
         outs = self._run_members(self.members(), X, self.image_train, image_test, device=device,
-                                 autocast=autocast, forced_dtype=self.force_inference_dtype, model=self.model)
+                                 autocast=autocast, forced_dtype=self.force_inference_dtype, model=self.model,
+                                 embeddings=embeddings)
         for out, cfg in zip(outs, self.ensemble_configs):
             yield out, cfg
 
@@ -348,7 +376,9 @@ class InferenceEngineOnDemand(InferenceEngine):
                    static_seed=static_seed, n_workers=n_workers, model=model,
                    force_inference_dtype=force_inference_dtype)
 
-    def iter_outputs(self, X, image_test, *, device: torch.device, autocast: bool) -> Iterator[tuple]:
+    def iter_outputs(self, X, image_test, *, device: torch.device, autocast: bool,
+                     embeddings: str | None = None) -> Iterator[tuple]:
+        check_embedding_source(embeddings)
         _, rng = infer_random_state(self.static_seed)
         itr = fit_preprocessing(configs=self.ensemble_configs, X_train=self.X_train, y_train=self.y_train,
                                 random_state=rng, cat_ix=self.cat_ix, n_workers=self.n_workers,
@@ -358,7 +388,7 @@ class InferenceEngineOnDemand(InferenceEngine):
             X = X.host()
         self.model = self.model.to(device)
         outs = self._run_members(members, X, self.image_train, image_test, device=device, autocast=autocast,
-                                 forced_dtype=self.force_inference_dtype, model=self.model)
+                                 forced_dtype=self.force_inference_dtype, model=self.model, embeddings=embeddings)
         for out, m in zip(outs, members):
             yield out, m.config
 
@@ -419,7 +449,9 @@ class InferenceEngineCacheKV(InferenceEngine):
         ex.compile_programs(preprocessors, X_train)
         return ex
 
-    def iter_outputs(self, X, image_test, *, device: torch.device, autocast: bool) -> Iterator[tuple]:
+    def iter_outputs(self, X, image_test, *, device: torch.device, autocast: bool,
+                     embeddings: str | None = None) -> Iterator[tuple]:
+        check_embedding_source(embeddings, cached=True)
         eng = self.model.engine(self.model._device() if device.type != "cuda" else device)
         tokens = None
         if image_test is not None and self.model.mixer_type in ("MGM", "MGM+CAP", "MoE") and self.mine:
@@ -440,10 +472,12 @@ class InferenceEngineCacheKV(InferenceEngine):
                     Xh = X if dev is None else dev.host()
                     xt = torch.from_numpy(np.asarray(self.preprocessors[i].transform(Xh).X, np.float32))
             xts.append(xt)
-        outs = dict(zip(self.mine, eng.cache_predict_many([self.caches[i] for i in self.mine], xts, tokens)))
+        res = eng.cache_predict_many([self.caches[i] for i in self.mine], xts, tokens, embeddings=embeddings)
+        outs = dict(zip(self.mine, res if embeddings is None else [r[2] for r in res]))
         if self.mine:
             eng.status()
         Q = len(X) if X is not None else len(image_test)
-        for out, cfg in zip(self.gather(outs, eng.device, Q, self.model.cfg.n_out), self.ensemble_configs):
+        width = self.model.cfg.n_out if embeddings is None else self.model.cfg.emsize
+        for out, cfg in zip(self.gather(outs, eng.device, Q, width), self.ensemble_configs):
             yield out, cfg
 

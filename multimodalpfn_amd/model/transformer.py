@@ -347,8 +347,13 @@ class PerFeatureTransformer(nn.Module):
         return _lib.f32_precision()
 
     # ------------------------------------------------------------------ forward
-    def forward(self, *args: Any, **kwargs: Any) -> torch.Tensor:
-        """Inference call forms of transformer.py:462-545 (4-tuple and 3-tuple)."""
+    def forward(self, *args: Any, **kwargs: Any) -> torch.Tensor | dict:
+        """Inference call forms of transformer.py:462-545 (4-tuple and 3-tuple).
+
+        ``only_return_standard_out=False`` returns the reference's dict (transformer.py:850-864): ``standard``
+        ``[Q, 1, n_out]`` (the logits of the plain call, bit for bit), ``train_embeddings`` ``[N, 1, E]`` and
+        ``test_embeddings`` ``[Q, 1, E]``, the target token's final state of the train and the test rows (fp32);
+        a cached-trainset call has no train rows, so its ``train_embeddings`` is ``[0, 1, E]``."""
         supported = {"only_return_standard_out", "style", "data_dags", "categorical_inds", "single_eval_pos",
                      "mixer_tokens", "precision"}
         spurious = set(kwargs) - supported
@@ -361,8 +366,7 @@ class PerFeatureTransformer(nn.Module):
         else:
             raise ValueError("Unrecognized input. Please follow the doc string.")
         assert style is None
-        if not kwargs.get("only_return_standard_out", True):
-            raise NotImplementedError("only the standard decoder output is served by the engine")
+        want_all = not kwargs.get("only_return_standard_out", True)
         sep = kwargs.get("single_eval_pos")
         dev = self._device()
         eng = self.engine(dev)
@@ -391,6 +395,9 @@ class PerFeatureTransformer(nn.Module):
                     "single_eval_pos=None needs a train-KV cache: call the model once on the train rows only "
                     "(single_eval_pos=len(X_train), as InferenceEngineCacheKV.prepare does) with "
                     "cache_trainset_representation=True")
+            if want_all:
+                logits, _, test_emb = eng.cache_predict(cache, x, tokens, embeddings="test")
+                return self._all_outputs(logits, test_emb.new_empty((0, test_emb.shape[1])), test_emb)
             return eng.cache_predict(cache, x, tokens).unsqueeze(1)
         if y.dim() > 1:
             y = y.reshape(-1)
@@ -400,12 +407,24 @@ class PerFeatureTransformer(nn.Module):
             # train rows only (InferenceEngineCacheKV.prepare, inference.py:425-436): keep this
             # member's head-0 K/V per layer and encoder statistics on the device; the reference
             # returns the (empty) test-row output
+            if want_all:
+                raise NotImplementedError(
+                    "the train-only cache-building call (cache_trainset_representation=True, single_eval_pos == "
+                    "number of rows) serves the standard output only: a train-KV cache keeps no train rows' embeddings")
             if self._train_cache is not None:
                 self._train_cache.free()
             self._train_cache = eng.cache_build(x, tokens, y, prec)
             return torch.empty((0, 1, self.cfg.n_out), device=dev, dtype=torch.float32)
+        if want_all:
+            return self._all_outputs(*eng.forward(x, tokens, y, prec, embeddings="both"))
         logits = eng.forward(x, tokens, y, prec)
         return logits.unsqueeze(1)
+
+    @staticmethod
+    def _all_outputs(logits: torch.Tensor, train_emb: torch.Tensor, test_emb: torch.Tensor) -> dict:
+        """The ``only_return_standard_out=False`` dict in the reference's shapes (batch axis of one in the middle)."""
+        return {"standard": logits.unsqueeze(1), "train_embeddings": train_emb.unsqueeze(1),
+                "test_embeddings": test_emb.unsqueeze(1)}
 
     def empty_trainset_representation_cache(self) -> None:
         """transformer.py:999-1001: drop the train-KV cache."""

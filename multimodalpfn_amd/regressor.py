@@ -25,7 +25,12 @@ import torch
 from sklearn.base import BaseEstimator, RegressorMixin, check_is_fitted
 
 from multimodalpfn_amd.bar_distribution import FullSupportBarDistribution, border_tables
-from multimodalpfn_amd.base import create_inference_engine, determine_precision, initialize_mmpfn_model
+from multimodalpfn_amd.base import (
+    EmbeddingsMixin,
+    create_inference_engine,
+    determine_precision,
+    initialize_mmpfn_model,
+)
 from multimodalpfn_amd.constants import ModelInterfaceConfig
 from multimodalpfn_amd.device_transform import device_table, plan_front_encoder
 from multimodalpfn_amd.model.preprocessing import ReshapeFeatureDistributionsStep
@@ -49,7 +54,7 @@ from multimodalpfn_amd.utils import (
 DEFAULT_QUANTILES = [0.1, 0.2, 0.3, 0.4, 0.5, 0.6, 0.7, 0.8, 0.9]  # regressor.py:631-632
 
 
-class MMPFNRegressor(RegressorMixin, BaseEstimator):
+class MMPFNRegressor(EmbeddingsMixin, RegressorMixin, BaseEstimator):
     """Multimodal PFN regressor (tabular + image/text embeddings), MI355X engine."""
 
     _OUTPUT_TYPES_BASIC = ("mean", "median", "mode")
@@ -254,6 +259,8 @@ class MMPFNRegressor(RegressorMixin, BaseEstimator):
         X = validate_X_predict(X, self)
         X = _fix_dtypes(X, cat_indices=self.categorical_features_indices)
         return self.preprocessor_.transform(X)
+
+    _encode_for_predict = _encode_host  # (EmbeddingsMixin)
 
     def predict_device(self, X, image_test: np.ndarray | None, *, quantiles: Sequence[float] = (),
                        want_logits: bool = False, targets=None) -> dict:
